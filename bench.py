@@ -14,7 +14,29 @@ Data: synthetic CIFAR-10-shaped uint8 images (class-conditional templates +
 noise), Dirichlet(0.5) non-IID shards (seed 102) -- no network access for the
 real dataset.  Weights are random-init ResNet-18 (11,173,962 params).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps and
+the result line.  ``--full`` adds everything else the benchmark measures: the uniform-sampling
+loop behind ``sampler_overhead_pct``, the untimed diagnostic steps (device-phase times, the DP
+communicator's view, the replica check) and the solo graph times.
+
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy``, the same
+from run to run up to bf16 rounding, so two builds can be compared output for output.  That
+needs care, because training is chaotic here: the kernels sum BN statistics and weight
+gradients with float atomics, so one forward already moves a scored loss in its last bf16
+digits (<= 1e-2 on losses of 2-4, measured on MI355X), Adam turns last-bit noise in a
+near-zero gradient into a +-lr parameter step, and from the second step on two identical runs
+draw different batches.  So with ``--dump-outputs`` the clock stops before the last timed
+step, the engine is put back to its seeded initial state (parameters, optimizer moments, BN
+running statistics, EMA, counters, meters) and primed, and the clock runs again for that one
+step: all N steps are timed, and the last one computes from inputs that are identical in
+every run.  Written are the float results of that step that rounding noise moves only by
+rounding: the 320 pool losses of its scoring forward, the BN running statistics it updated
+(train batch + pool), and the pool mean and loss EMA.  Left out are the parameters (the +-lr
+steps above), the integer results (drawn slots, shard indices, correct count), which a
+last-digit difference can flip, and the trained batch's loss sum, which follows the drawn
+slots (one other sample of 32: 1-2 %, measured).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 """
 from __future__ import annotations
@@ -162,6 +184,71 @@ def solo_graph_ms(eng, reps=5):
             'tail': t(lambda: g['tail'].replay())}
 
 
+DUMP_BUDGET_BYTES = 48 << 20    # per array; the whole dump stays under 64 MB
+
+
+def snapshot_state(eng):
+    """The engine's seeded initial state (taken before ``prime()``): everything a step reads
+    that an earlier step wrote."""
+    s = {'p': eng.opt.p.clone(), 'ctrl': eng.ctrl.clone(), 'ema': eng.ema.clone(),
+         'meters': eng.meters.clone(),
+         'bn': [(u.bn.running_mean.clone(), u.bn.running_var.clone(),
+                 u.bn.num_batches_tracked.clone()) for u in eng.units]}
+    if eng.table is not None:
+        s['table'] = (eng.table.importance.clone(), eng.table.group.clone())
+    return s
+
+
+def restore_state(eng, s):
+    """Put the engine back to ``snapshot_state`` in place (captured graphs keep their
+    pointers) and prime it: a fresh pool scored, the first batch drawn and gathered."""
+    import torch
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        eng.opt.p.copy_(s['p'])
+        eng.opt.pack_weights()
+        for buf in (eng.opt.m, eng.opt.v, eng.opt.g):
+            buf.zero_()
+        for u, (mean, var, n) in zip(eng.units, s['bn']):
+            u.bn.running_mean.copy_(mean)
+            u.bn.running_var.copy_(var)
+            u.bn.num_batches_tracked.copy_(n)
+        eng.ctrl.copy_(s['ctrl'])
+        eng.ema.copy_(s['ema'])
+        eng.meters.copy_(s['meters'])
+        if eng.table is not None:
+            eng.table.importance.copy_(s['table'][0])
+            eng.table.group.copy_(s['table'][1])
+    eng.prime()
+    torch.cuda.synchronize()
+
+
+def dump_outputs(eng, path):
+    """The float results of the last timed step (see the module docstring) as float32 /
+    float64 ``.npy`` files: pool losses, BN running statistics, pool mean + EMA.  An array over the
+    budget is cut to a fixed, seeded sample of its elements."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    m = eng.read_meters()
+    arrays = {
+        'pool_losses': eng.score_mode.losses.detach().float().cpu().numpy(),
+        'bn_running_mean': torch.cat([u.bn.running_mean.detach().float().reshape(-1)
+                                      for u in eng.units]).cpu().numpy(),
+        'bn_running_var': torch.cat([u.bn.running_var.detach().float().reshape(-1)
+                                     for u in eng.units]).cpu().numpy(),
+        'pool_mean_ema': np.asarray([m['pool_mean'], m['ema']], np.float64),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        if a.nbytes > DUMP_BUDGET_BYTES:
+            keep = np.random.RandomState(0).choice(a.size, DUMP_BUDGET_BYTES // a.itemsize,
+                                                   replace=False)
+            a = a[np.sort(keep)]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -189,7 +276,16 @@ def main():
                     help='profiling aid: after warm-up, replay only this step graph --steps '
                          'times (no concurrent stream) and print its time per replay')
     ap.add_argument('--diag-steps', type=int, default=5,
-                    help='untimed steps after the timed loop with device-phase events')
+                    help='with --full: untimed steps after the timed loop with device-phase '
+                         'events')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the sampler overhead (a second, uniform-sampling timed '
+                         'loop) and run the untimed diagnostics (device phases, DP view, '
+                         'replica check, solo graph times)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 '
+                         '/ float64); that step then starts from the seeded initial state, '
+                         'so its results are the same in every run up to rounding')
     args = ap.parse_args()
     # stdout carries exactly ONE line, the result JSON: everything else written to fd 1 while the
     # job runs (RCCL's version banner at communicator init, library warnings) goes to stderr
@@ -237,7 +333,7 @@ def main():
             eng.broadcast_from(0)
         return eng
 
-    def run(eng, steps, warmup, scoring=True):
+    def run(eng, steps, warmup, scoring=True, before_last=None):
         eng.scoring = scoring
         eng.prime()
         eng.step()
@@ -245,16 +341,27 @@ def main():
             eng.build_graphs()
         for _ in range(warmup):
             eng.step()
-        torch.cuda.synchronize()
-        if ws > 1:
-            dist.barrier()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            eng.step()
-        torch.cuda.synchronize()
-        if ws > 1:
-            dist.barrier()
-        dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=device)
+
+        def timed(n):
+            torch.cuda.synchronize()
+            if ws > 1:
+                dist.barrier()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                eng.step()
+            torch.cuda.synchronize()
+            if ws > 1:
+                dist.barrier()
+            return time.perf_counter() - t0
+
+        if before_last is None or steps < 1:
+            t = timed(steps)
+        else:
+            # (--dump-outputs: the clock stops while the engine goes back to its initial state)
+            t = timed(steps - 1)
+            before_last()
+            t += timed(1)
+        dt = torch.tensor([t], dtype=torch.float64, device=device)
         if ws > 1:
             dist.all_reduce(dt, op=dist.ReduceOp.MAX)
         return float(dt.item())
@@ -274,14 +381,28 @@ def main():
                                       'ms_per_replay': round((time.perf_counter() - t0) * 1e3 /
                                                              args.steps, 4)}) + '\n').encode())
         return
-    t_is = run(eng, args.steps, args.warmup)
-    m = eng.read_meters()
-    diag = diagnostics(eng, args.diag_steps, ws)
+    if args.dump_outputs:
+        seen = {}
+        state0 = snapshot_state(eng)
+
+        def before_last():
+            seen.update(eng.read_meters())      # the restore clears the meters
+            restore_state(eng, state0)
+        t_is = run(eng, args.steps, args.warmup, before_last=before_last)
+        m = eng.read_meters()
+        for k in ('loss_sum', 'count'):
+            m[k] += seen.get(k, 0.0)
+        if rank == 0:
+            dump_outputs(eng, args.dump_outputs)
+    else:
+        t_is = run(eng, args.steps, args.warmup)
+        m = eng.read_meters()
+    diag = diagnostics(eng, args.diag_steps, ws) if args.full else {}
     ms = t_is * 1e3 / args.steps
     value = ws * args.batch * args.steps / t_is
     overhead = None
     eng_u = None
-    if not args.no_overhead:
+    if args.full and not args.no_overhead:
         eng.close()                      # deterministic teardown before the next engine
         eng_u = make(False)
         t_u = run(eng_u, args.steps, args.warmup, scoring=False)

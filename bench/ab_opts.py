@@ -2,10 +2,10 @@
 
     python bench/ab_opts.py --out ab.json --rounds 3 "" "persist_bn=1" "hconv_row=0"
 
-Runs ``bench.py --no-overhead`` once per option string per round (MERCURY_ENGINE_OPTS set to the
-string; "" = defaults), interleaved so clock / thermal drift hits every arm alike, and writes
-ms/step and solo graph times per arm.  The parent process never touches the GPU (each run is a
-child process)."""
+Runs ``bench.py --full --no-overhead`` once per option string per round (MERCURY_ENGINE_OPTS set
+to the string; "" = defaults), interleaved so clock / thermal drift hits every arm alike, and
+writes ms/step and solo graph times per arm.  The parent process never touches the GPU (each
+run is a child process)."""
 import argparse
 import json
 import os
@@ -29,7 +29,7 @@ def main():
         for o in args.opts:
             env = dict(os.environ, MERCURY_ENGINE_OPTS=o)
             cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(args.steps),
-                   '--warmup', '30', '--no-overhead', '--config', args.config]
+                   '--warmup', '30', '--full', '--no-overhead', '--config', args.config]
             p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=args.timeout)
             if p.returncode != 0:
                 sys.stderr.write(p.stderr[-3000:])

@@ -81,14 +81,14 @@ def job_bench(o, a):
     variants = [v.strip() for v in (a.args or '').split(';')] if a.args else ['']
     for i, v in enumerate(variants):
         out = os.path.join(o, 'bench%d.json' % i)
-        run([PY, 'bench.py'] + shlex.split(v), out, 400)
+        run([PY, 'bench.py', '--full'] + shlex.split(v), out, 400)
         tail(out, 1)
 
 
 def job_session(o, a):
     job_tests(o, a)
-    for i, v in enumerate(['--steps 200 --warmup 20',
-                           '--steps 100 --warmup 10 --no-overhead --force-buckets']):
+    for i, v in enumerate(['--full --steps 200 --warmup 20',
+                           '--full --steps 100 --warmup 10 --no-overhead --force-buckets']):
         out = os.path.join(o, 'bench%d.json' % i)
         run([PY, 'bench.py'] + v.split(), out, 400)
         tail(out, 1)
@@ -145,7 +145,7 @@ def job_presets(o, a):
         out = os.path.join(o, c + '.json')
         extra = ['--steps', '300', '--warmup', '30'] if c == 'resnet18-cifar10' else \
             ['--steps', '100', '--warmup', '10', '--no-overhead']
-        run([PY, 'bench.py', '--config', c] + extra, out, 400)
+        run([PY, 'bench.py', '--full', '--config', c] + extra, out, 400)
         tail(out, 1)
 
 
@@ -158,7 +158,7 @@ def job_ab(o, a):
             kv = dict(x.split('=', 1) for x in e.split())
             out = os.path.join(o, 'v%d_%d.json' % (j + 1, rnd + 1))
             run([PY, 'bench.py'] + shlex.split(a.args or '') +
-                ['--steps', '300', '--warmup', '30', '--no-overhead'], out, 200, env=kv)
+                ['--full', '--steps', '300', '--warmup', '30', '--no-overhead'], out, 200, env=kv)
             with open(out) as f:
                 d = json.loads(f.read().strip().splitlines()[-1])
             res[e].append(d['ms_per_step'])

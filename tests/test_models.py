@@ -1,20 +1,23 @@
-import importlib.util
-import os
-
 import pytest
 import torch
 
 from mercury_amd.models import (MobileNetV2, MyLSTM, ResNet18, ResNet34, ResNet50,
                                 ResNet50_ImageNet, ResNet101, VGG)
-from refutil import REF, needs_ref
+from refutil import golden, interchange_input
 
 
-def _ref_models():
-    spec = importlib.util.spec_from_file_location('ref_pytorch_model',
-                                                  os.path.join(REF, 'pytorch_model.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+def _check_interchange(name, ours):
+    """Keys, order and shapes of the reference's state dict, and its output with OUR weights
+    loaded into it (recorded in float64 from the same seeded weights and input)."""
+    ref = golden('interchange_' + name)
+    ours = ours.double()
+    a = ours.state_dict()
+    assert list(a.keys()) == [str(k) for k in ref['keys']]
+    assert [','.join(str(d) for d in a[k].shape) for k in a] == [str(s) for s in ref['shapes']]
+    ours.eval()
+    with torch.no_grad():
+        assert torch.allclose(ours(interchange_input(name)), torch.from_numpy(ref['out']),
+                              atol=1e-5)
 
 
 def test_param_counts():
@@ -25,35 +28,16 @@ def test_param_counts():
     assert len(ResNet18(10).state_dict()) == 122
 
 
-@needs_ref
 @pytest.mark.parametrize('name', ['ResNet18', 'ResNet34', 'ResNet50'])
 def test_resnet_state_dict_interchange(name):
-    ref = _ref_models()
     torch.manual_seed(0)
-    ours = {'ResNet18': ResNet18, 'ResNet34': ResNet34, 'ResNet50': ResNet50}[name](10)
-    theirs = getattr(ref, name)(10)
-    a, b = ours.state_dict(), theirs.state_dict()
-    assert list(a.keys()) == list(b.keys())
-    assert all(a[k].shape == b[k].shape for k in a)
-    theirs.load_state_dict(a)
-    ours.eval()
-    theirs.eval()
-    x = torch.randn(2, 3, 32, 32)
-    with torch.no_grad():
-        assert torch.allclose(ours(x), theirs(x), atol=1e-5)
+    _check_interchange(name, {'ResNet18': ResNet18, 'ResNet34': ResNet34,
+                              'ResNet50': ResNet50}[name](10))
 
 
-@needs_ref
 def test_vgg_interchange():
-    ref = _ref_models()
-    ours, theirs = VGG('VGG11', 30), ref.VGG('VGG11', 30)
-    assert list(ours.state_dict()) == list(theirs.state_dict())
-    theirs.load_state_dict(ours.state_dict())
-    ours.eval()
-    theirs.eval()
-    x = torch.randn(2, 1, 101, 161)
-    with torch.no_grad():
-        assert torch.allclose(ours(x), theirs(x), atol=1e-5)
+    torch.manual_seed(0)
+    _check_interchange('VGG11', VGG('VGG11', 30))
 
 
 def test_lstm_runs_and_backprops():

@@ -3,27 +3,21 @@ import torch
 
 from mercury_amd.utils import (Accuracy, Average, EMAverage, flatten, flatten_torch_tensor,
                                quantize_tensor, unflatten, unflatten_torch_tensor)
-from refutil import extract, needs_ref
+from refutil import METER_UPDATES, golden
 
 
-@needs_ref
 def test_meters_match_reference():
-    ns = extract('util.py', {'Average', 'EMAverage', 'Accuracy'}, {'torch': torch})
-    ra, rb = ns['Average'](), Average()
-    re_, rm = ns['EMAverage'](), EMAverage()
-    for v, n in [(1.0, 32), (0.5, 16), (2.0, 8)]:
-        ra.update(v, n)
+    ref = golden('meters')
+    rb, rm = Average(), EMAverage()
+    for v, n in METER_UPDATES:
         rb.update(v, n)
-        re_.update(v)
         rm.update(v)
-    assert str(ra) == str(rb)
-    assert abs(re_.value - rm.value) < 1e-12 and str(re_) == str(rm)
-    out = torch.randn(64, 10)
-    lab = torch.randint(0, 10, (64,))
-    r, m = ns['Accuracy'](), Accuracy()
-    r.update(out, lab)
+    assert str(ref['str_average']) == str(rb)
+    assert abs(float(ref['ema_value']) - rm.value) < 1e-12 and str(ref['str_ema']) == str(rm)
+    out, lab = torch.from_numpy(ref['out']), torch.from_numpy(ref['lab'])
+    m = Accuracy()
     m.update(out, lab)
-    assert str(r) == str(m) and r.accuracy == m.accuracy
+    assert str(ref['str_accuracy']) == str(m) and float(ref['accuracy']) == m.accuracy
 
 
 def test_average_device_lazy():
