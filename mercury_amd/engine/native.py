@@ -33,12 +33,9 @@ import torch.distributed as dist
 
 from .. import ops
 from ..ops import hconv, tune
-from ..ops.conv import (ConvSpec, cpad8, dgrad_plan, fwd_plan, pgemm_ok, pgemm_plain_wins,
-                        pgemm_plan, pgemm_pro_wins, pro_plan, pwconv_ok, pwconv_plain_wins,
-                        pwconv_pro_wins, slab_bytes,
-                        stem_ok, wgrad_plan)
-from ..ops.conv import pro_ok as conv_pro_ok
+from ..ops.conv import cpad8, slab_bytes
 from ..parallel.buckets import default_bucket_bytes
+from . import schedule
 
 _RELEASE = []    # (hipGraphExec_t, [hipEvent_t]) of un-closed collected engines
 
@@ -87,22 +84,44 @@ BN_EPS = 1e-5
 
 
 class _Mode(object):
-    """Per-batch-size buffers: activations, stats, plans, slabs."""
+    """Per-batch-size buffers (activations, stats, slabs), plans and launch schedules."""
 
-    def __init__(self, name, N, group_imgs, train):
+    def __init__(self, name, mp, lw, opts):
         self.name = name
-        self.N = N
-        self.group_imgs = group_imgs   # images per BN stat group (0 = whole batch)
-        self.train = train
-        self.spec = {}
-        self.plan = {}
+        self.mp = mp                     # schedule.ModePlan (``spec`` / ``plan`` are its dicts)
+        self.lw, self.opts = lw, opts
+        self.N = mp.N
+        self.group_imgs = mp.group_imgs  # images per BN stat group (0 = whole batch)
+        self.train = mp.train
+        self.spec = mp.spec
+        self.plan = mp.plan
         self.buf = {}
         self.stats = {}
         self.slab = None
-        self.G = 1 if not group_imgs else N // group_imgs
-        self.prereduced = {}             # block index -> BN sums already reduced by a dgrad
+        self.G = mp.G
+        self.head_bn = None
+        self.head_reduced = False        # the head's backward reduced the last BN's sums
         self.dw_region = {}              # depthwise unit -> (slab offset, floats, wgrad blocks)
         self.dw_pending = []             # deferred depthwise wgrad reduces of this backward
+
+    def resolve(self):
+        """(Re-)resolve the launch schedules from the plans as they stand: at mode build, and
+        again whenever a plan changed (ops/step_tune.py) or graphs are captured, so that a
+        schedule never describes plans that are gone.  A dual forward pair whose plans both
+        split K gets the shortcut's slab here (never from inside ``forward``)."""
+        schedule.apply_globals(self.opts)
+        self.fwd_steps = schedule.forward_schedule(self.lw, self.mp, self.opts)
+        self.bwd = schedule.backward_schedule(self.lw, self.mp, self.opts) if self.train \
+            else None
+        for s in self.fwd_steps:
+            pa, pb = self.plan.get((s.unit, 'fwd')), self.plan.get((s.unit2, 'fwd'))
+            if s.op == 'dual_conv' and pa[2] > 1 and pb[2] > 1:
+                # the shortcut's split-K partials and tile counters get a slab of their own
+                sp = self.spec[s.unit2]
+                need = (slab_bytes(sp.M, sp.K, *pb[:3]) + 3) // 4
+                if (s.unit2, 'slab') not in self.buf or self.buf[s.unit2, 'slab'].numel() < need:
+                    self.buf[s.unit2, 'slab'] = torch.zeros(need, dtype=torch.float32,
+                                                            device=self.slab.device)
 
 
 class NativeEngine(object):
@@ -195,6 +214,7 @@ class NativeEngine(object):
         self.units = []
         for blk in self.lw.blocks:
             self.units += blk.units + ([blk.shortcut] if blk.shortcut else [])
+        self.unit = {u.name: u for u in self.units}
         # conv bias (speech VGG) is added in the conv epilogue; under train-mode BN its gradient
         # is exactly zero (the batch mean absorbs it), so its grad segment is never written
         self._make_params(optimizer, lr, betas, eps, weight_decay, momentum)
@@ -215,23 +235,9 @@ class NativeEngine(object):
         self.shard = None
         self.primed = False              # a scored pool / drawn batch is pending
         self.scoring = True
-        self.fuse_bn_bwd = True          # BN-backward reduce in the dgrad epilogue
         self.roctx = False               # per-phase roctx ranges around the step's host calls
-        self.pair_bwd = True             # dgrad + wgrad of a conv in one launch
-        # kernel-path switches (config.EngineOptions: defaults = the measured-best paths, each
-        # with the A/B that keeps it)
-        o = self.opts
-        self.fuse_bn_fwd = o.fuse_bn_fwd
-        self.use_hconv = o.hconv
-        self.use_pgemm = o.pgemm
-        self.use_pwconv = o.pwconv
-        self.use_stem = o.stem
-        self.dw_pro = o.dw_pro
-        self.res_pro = o.fuse_bn_fwd and o.res_pro
-        self.head_bw = o.head_bw
-        self.dw_pair = o.dw_pair
-        self.persist_bn = o.persist_bn if o.persist_bn in ('0', '1', 'row', 'stat') else (
-            '1' if str(o.persist_bn).lower() in ('true', 'on', 'yes') else '0')
+        # (the kernel-path switches of config.EngineOptions -- defaults = the measured-best
+        # paths, each with the A/B that keeps it -- are read by engine/schedule.py)
         self._apply_globals()
 
         if sampler not in ('alias', 'cdf', 'groupwise'):
@@ -286,8 +292,8 @@ class NativeEngine(object):
         persistent grid / waves / plan overrides, the stride-2 dgrad switch) are re-applied by
         every phase of THIS engine that reads them -- plan building (set_shard / mode), eager
         launches and graph capture -- so engines with different options can share a process."""
-        hconv.configure(self.opts)
-        ops.conv.DGRAD_S2 = self.opts.dgrad_s2
+        schedule.apply_globals(self.opts)
+        hconv.configure_launcher()
 
     # ------------------------------------------------------------------ parameters
     def _final_chw(self):
@@ -387,17 +393,15 @@ class NativeEngine(object):
 
     # ------------------------------------------------------------------ buffers
     def mode(self, name, N=None, group_imgs=0, train=False):
+        """Plan the mode (engine/schedule.py), allocate its buffers from the plan's sizes,
+        resolve its launch schedules."""
         if name in self.modes:
             return self.modes[name]
         self._apply_globals()
-        m = _Mode(name, N, group_imgs, train)
+        mp = schedule.plan_mode(self.lw, self.opts, N, self.H, self.W, group_imgs, train)
+        m = _Mode(name, mp, self.lw, self.opts)
         dev = self.device
-        H, W = self.H, self.W
-        C = cpad8(self.lw.in_channels)
-        slab = 0
         dw_slab = 0
-        coef = 0
-        nstats = 0
         nsums = 0
         bf = torch.bfloat16
 
@@ -405,16 +409,9 @@ class NativeEngine(object):
             return torch.empty(M * K, dtype=bf, device=dev)
 
         for bi, blk in enumerate(self.lw.blocks):
-            h, w = H, W
-            main_hw = None
             for u in blk.units + ([blk.shortcut] if blk.shortcut else []):
-                if u is blk.shortcut:
-                    main_hw = (h, w)
-                    h, w = H, W          # the shortcut reads the block input
-                sp = ConvSpec(N, h, w, u.C, u.K, u.R, u.R, u.stride, u.pad)
-                if group_imgs:
-                    sp.group_rows = group_imgs * sp.P * sp.Q
-                m.spec[u.name] = sp
+                sp = m.spec[u.name]
+                inner = u is not blk.units[-1] and u is not blk.shortcut
                 if u.depthwise and train:
                     # per-block weight-gradient partials (summed by a reduce kernel), a region
                     # per layer so the reduces can be deferred and batched at the end of the
@@ -422,113 +419,56 @@ class NativeEngine(object):
                     m.dw_region[u.name] = (dw_slab, ops.dwconv_wgrad_slab_floats(
                         N, sp.P, sp.Q, sp.C), ops.dwconv_wgrad_blocks(N, sp.P, sp.Q, sp.C))
                     dw_slab += m.dw_region[u.name][1]
-                if not u.depthwise:
-                    # measured-best plans from the tuning cache (ops/tune.py) when present
-                    # the scoring pass runs beside the latency-bound train chain: fewer, larger
-                    # tiles leave the train kernels more room (measured, ResNet-18: 128-block
-                    # target 1.656 vs 256-block 1.667 ms/step; split-K or 512 blocks slower)
-                    mb = self.opts.score_min_blocks if group_imgs else 0
-                    m.plan[u.name, 'fwd'] = p = tune.fwd_plan_for(
-                        sp, fwd_plan(sp, min_blocks=mb) if mb else fwd_plan(sp))
-                    slab = max(slab, slab_bytes(sp.M, sp.K, *p[:3]))
-                    pp = pro_plan(sp) if self.opts.pro_plans else None
-                    if pp is not None:
-                        # the plan it runs with when it takes its input's BN in the prologue
-                        m.plan[u.name, 'fwd_pro'] = pp
-                        slab = max(slab, slab_bytes(sp.M, sp.K, *pp))
-                    if self.use_pgemm and pgemm_ok(sp) and u.b_seg is None:
-                        m.plan[u.name, 'pgemm'] = pgemm_plan(sp)
-                        coef = max(coef, m.G * 2 * sp.Cp)
-                    if self.use_stem and stem_ok(sp) and bi == 0 and u is blk.units[0]:
-                        m.plan[u.name, 'stem'] = True
-                    if self.use_pwconv and pwconv_ok(sp) and u.b_seg is None:
-                        m.plan[u.name, 'pwconv'] = True
-                        coef = max(coef, m.G * 2 * sp.Cp)
-                    # stride-1 3x3 convs on the halo-tile kernel where it measured faster
-                    uh = self.use_hconv == '1' or self.use_hconv == ('train' if train else 'score')
-                    hp = hconv.engine_plan(sp, bias=u.b_seg is not None,
-                                           train=train) if uh else None
-                    if hp is not None:
-                        m.plan[u.name, 'hconv'] = hp
-                        slab = max(slab, slab_bytes(sp.M, sp.K, *hp[:3]))
-                    # scoring pass: an intra-block conv on the persistent kernel takes its
-                    # input's BN + activation in the halo staging (no residual there)
-                    hb = None
-                    if not train and group_imgs and self.persist_bn != '0' and \
-                            u is not blk.units[0] and u is not blk.shortcut:
-                        hb = hconv.persist_bn_plan(sp, group_imgs,
-                                                   row_only=self.persist_bn in ('row', 'stat'),
-                                                   stat_only=self.persist_bn == 'stat')
-                    if hb is not None:
-                        m.plan[u.name, 'hconv_bn'] = hb
-                        slab = max(slab, slab_bytes(sp.M, sp.K, *hb[:3]))
-                    if train:
-                        if u.need_dgrad and sp.K % 8 == 0:
-                            dp, wp = tune.bwd_plans_for(sp, dgrad_plan(sp), wgrad_plan(sp))
-                        else:
-                            dp, wp = dgrad_plan(sp), wgrad_plan(sp)
-                        if u.need_dgrad:
-                            m.plan[u.name, 'dgrad'] = dp
-                            slab = max(slab, slab_bytes(N * h * w, sp.Cp, *dp))
-                        m.plan[u.name, 'wgrad'] = wp
                 m.buf[u.name, 'y'] = act(sp.M, u.K)
-                m.stats[u.name] = nstats
-                nstats += m.G * 2 * u.K
-                if u is not blk.units[-1] and u is not blk.shortcut:
+                if inner:
                     m.buf[u.name, 'a'] = act(sp.M, u.K)
                 if train:
                     m.buf[u.name, 'dy'] = act(sp.M, u.K)
                     m.buf[u.name, 'sums'] = nsums
                     nsums += ops.sums_numel(u.K)      # [SUMS_R][3][K] replicas
-                    if u is not blk.units[-1] and u is not blk.shortcut:
+                    if inner:
                         m.buf[u.name, 'da'] = act(sp.M, u.K)
-                if u is not blk.shortcut:
-                    h, w = sp.P, sp.Q
-            if main_hw is not None:
-                h, w = main_hw
-            last = blk.units[-1]
-            K = last.K
-            m.buf[bi, 'out'] = act(N * h * w, K)
+            K = blk.units[-1].K
+            h, w = mp.hw[bi]
+            geom = mp.pool.get(bi)
+            rows = N * h * w if geom is None else N * geom[1] * geom[2]
+            m.buf[bi, 'out'] = act(rows, K)
             if train:
-                m.buf[bi, 'dout'] = act(N * h * w, K)
-            if blk.pool is not None:
-                k, st, pd = blk.pool
-                P_ = (h + 2 * pd - k) // st + 1
-                Q_ = (w + 2 * pd - k) // st + 1
+                m.buf[bi, 'dout'] = act(rows, K)
+            if geom is not None:
                 m.buf[bi, 'pre'] = m.buf[bi, 'out']
-                m.buf[bi, 'out'] = act(N * P_ * Q_, K)
-                m.buf[bi, 'pool_geom'] = (N, h, w, K, P_, Q_, k, st, pd)
+                m.buf[bi, 'out'] = act(N * h * w, K)
+                m.buf[bi, 'pool_geom'] = geom
                 if train:
-                    m.buf[bi, 'argmax'] = torch.empty(N * P_ * Q_ * K, dtype=torch.uint8,
+                    m.buf[bi, 'argmax'] = torch.empty(N * h * w * K, dtype=torch.uint8,
                                                       device=dev)
                     m.buf[bi, 'dpre'] = m.buf[bi, 'dout']
-                    m.buf[bi, 'dout'] = act(N * P_ * Q_, K)
-                h, w = P_, Q_
+                    m.buf[bi, 'dout'] = act(N * h * w, K)
             m.buf[bi, 'hw'] = (h, w)
-            H, W, C = h, w, K
-        m.stats_arena = torch.zeros(max(nstats, 1), device=dev)
+        m.stats_arena = torch.zeros(max(mp.nstats, 1), device=dev)
         m.sums_arena = torch.zeros(max(nsums, 1), device=dev)
-        for key, off in list(m.stats.items()):
-            u = next(x for x in self.units if x.name == key)
-            m.stats[key] = m.stats_arena[off:off + m.G * 2 * u.K]
+        for u in self.units:
+            off = mp.stats[u.name]
+            m.stats[u.name] = m.stats_arena[off:off + m.G * 2 * u.K]
             if train:
                 so = m.buf[u.name, 'sums']
                 m.buf[u.name, 'sums'] = m.sums_arena[so:so + ops.sums_numel(u.K)]
-        m.final_hw = H * W
-        m.final_C = C
+        m.final_hw = mp.final_hw
+        m.final_C = C = mp.final_C
         m.pooled = torch.zeros(N, C, device=dev)
         m.logits = torch.zeros(N, self.classes, device=dev)   # wide heads' FC output
         m.losses = torch.zeros(N, device=dev)
         if train:
             m.dlogits = torch.zeros(N, self.classes, device=dev)
-        m.slab = torch.zeros(max(1, (slab + 3) // 4), dtype=torch.float32, device=dev)
+        m.slab = torch.zeros(max(1, (mp.slab + 3) // 4), dtype=torch.float32, device=dev)
         m.dw_slab = torch.empty(dw_slab, dtype=torch.float32, device=dev) if dw_slab else None
         # per-stream scale / shift workspace of the pointwise GEMM's input prologue (each fused
         # conv's coefficient kernel fills it right before the conv, on the same stream)
-        m.coef = torch.zeros(max(1, coef), dtype=torch.float32, device=dev)
+        m.coef = torch.zeros(max(1, mp.coef), dtype=torch.float32, device=dev)
         m.input = torch.zeros(N, self.H, self.W, cpad8(self.lw.in_channels), dtype=bf, device=dev)
         m.label = torch.zeros(N, dtype=torch.int32, device=dev)
         m.index = torch.zeros(N, dtype=torch.int32, device=dev)
+        m.resolve()
         self.modes[name] = m
         return m
 
@@ -539,311 +479,133 @@ class NativeEngine(object):
     def _beta(self, u, grad=False):
         return self._pview(u.beta_seg, grad)
 
-    def _conv_fwd(self, m, u, x, y, stats, pro=None):
-        sp = m.spec[u.name]
-        if (u.name, 'stem') in m.plan and pro is None:
-            ops.stem_fwd(x, self.w_krsc[u.name], y, sp, stats=stats,
-                         bias=self._pview(u.b_seg) if u.b_seg is not None else None)
-            return
-        if pro is not None and pro.get('pw'):
-            ops.pwconv_fwd(x, self.w_krsc[u.name], y, sp, stats=stats, pro=pro)
-            return
-        if pro is None and (u.name, 'pwconv') in m.plan and pwconv_plain_wins(sp) and \
-                self.opts.pwconv_plain:
-            ops.pwconv_fwd(x, self.w_krsc[u.name], y, sp, stats=stats)
-            return
-        pg = m.plan.get((u.name, 'pgemm'))
-        if pg is not None and (pro is not None and pro.get('pg') or
-                               pro is None and pgemm_plain_wins(sp)):
-            ops.pgemm_fwd(x, self.w_krsc[u.name], y, sp, stats=stats, bn=pg, pro=pro)
-            return
-        if u.depthwise:
+    def _bn_desc(self, m, u, act, count=True, ghost=False, **extra):
+        """The BN of ``u`` + activation ``act`` as the descriptor its consumers take (a conv's
+        input prologue, the pool, the head, bn_apply): batch / ghost-group statistics (+ the
+        rows per group ``count``; ``ghost``: + the images per group) in train and scoring
+        modes, the running statistics in eval; ``extra``: the consumer's own keys."""
+        d = dict(gamma=self._gamma(u), beta=self._beta(u), act=act, eps=BN_EPS, **extra)
+        if m.train or m.group_imgs:
+            su = m.spec[u.name]
+            d['stats'] = m.stats[u.name]
+            if count:
+                d['count'] = su.group_rows or su.M
+            if ghost:
+                d['group_imgs'] = m.group_imgs
+        else:
+            d.update(rmean=u.bn.running_mean, rvar=u.bn.running_var)
+        return d
+
+    def _block_in(self, m, bi, x):
+        """Input of block ``bi`` in a forward that started from ``x``."""
+        return x if bi == 0 else m.buf[bi - 1, 'out']
+
+    def _pro(self, m, s, x):
+        """The input prologue of conv step ``s``: the BN + activation of ``s.src_unit`` applied
+        to its raw output while the conv loads it (csrc/igemm.h ProParams, pgemm / pwconv /
+        dwconv prologues, the halo staging of csrc/hconv.hip MODE 1)."""
+        if s.pro is None:
+            return None
+        u = self.unit[s.src_unit]
+        if s.pro == 'halo':
+            return self._bn_desc(m, u, s.act, group_imgs=m.group_imgs or m.N)
+        kw = dict(keep={None: None, 'a': m.buf.get((u.name, 'a')),
+                        'out': m.buf.get((s.block - 1, 'out'))}[s.keep])
+        if s.pro == 'dw':
+            kw.update(dw=True, group_imgs=m.group_imgs or m.N)
+        elif s.pro != 'igemm':
+            kw['res'] = self._block_in(m, s.block - 1, x) if s.res == 'in' else None
+        if s.pro in ('pg', 'pw'):
+            su = m.spec[u.name]
+            kw.update({s.pro: True}, coef=m.coef, group_rows=su.group_rows or su.M)
+        return self._bn_desc(m, u, s.act, **kw)
+
+    def _conv_fwd(self, m, name, route, x, pro=None):
+        """Conv unit ``name`` on the kernel ``route`` (schedule.route)."""
+        u, sp, y = self.unit[name], m.spec[name], m.buf[name, 'y']
+        stats = m.stats[name] if m.train or m.group_imgs else None
+        w = self.w_krsc.get(name)
+        bias = self._pview(u.b_seg) if u.b_seg is not None else None
+        if route == 'stem':
+            ops.stem_fwd(x, w, y, sp, stats=stats, bias=bias)
+        elif route == 'pwconv':
+            ops.pwconv_fwd(x, w, y, sp, stats=stats, pro=pro)
+        elif route == 'pgemm':
+            ops.pgemm_fwd(x, w, y, sp, stats=stats, bn=m.plan[name, 'pgemm'], pro=pro)
+        elif route == 'dwconv':
             ops.dwconv_fwd(x, self._pview(u.w_seg), y, sp.N, sp.H, sp.W, sp.C, sp.P, sp.Q,
                            sp.stride, sp.pad, stats=stats, group_rows=sp.group_rows or sp.M,
-                           pro=pro if pro is not None and pro.get('dw') else None)
-        elif pro is None and (u.name, 'hconv') in m.plan:
-            hconv.hconv_fwd(x, self.w_krsc[u.name], y, sp, m.plan[u.name, 'hconv'], stats=stats,
-                            slab=m.slab,
-                            bias=self._pview(u.b_seg) if u.b_seg is not None else None)
+                           pro=pro)
+        elif route == 'hconv':
+            hconv.hconv_fwd(x, w, y, sp, m.plan[name, 'hconv' if pro is None else 'hconv_bn'],
+                            stats=stats, slab=m.slab, bias=bias, pro=pro)
         else:
-            ops.conv_fwd(x, self.w_krsc[u.name], y, sp, stats=stats, slab=m.slab,
-                         plan=self._pro_plan(m, u) if pro is not None else m.plan[u.name, 'fwd'],
-                         bias=self._pview(u.b_seg) if u.b_seg is not None else None, pro=pro)
+            ops.conv_fwd(x, w, y, sp, stats=stats, slab=m.slab, bias=bias, pro=pro,
+                         plan=m.plan[name, 'fwd'] if pro is None else
+                         schedule.pro_plan_of(m.plan, name))
 
-    def _pro_plan(self, m, u):
-        """igemm plan of ``u`` when it applies its input's BN in the prologue."""
-        return m.plan.get((u.name, 'fwd_pro'), m.plan[u.name, 'fwd'])
-
-    def _igemm_only(self, m, u):
-        """True when _conv_fwd(m, u, ..., pro=None) runs u on the plain igemm kernel."""
-        if u.depthwise or u.b_seg is not None:
-            return False
-        if any((u.name, k) in m.plan for k in ('stem', 'hconv')):
-            return False
-        if (u.name, 'pwconv') in m.plan and pwconv_plain_wins(m.spec[u.name]) and \
-                self.opts.pwconv_plain:
-            return False
-        return not ((u.name, 'pgemm') in m.plan and pgemm_plain_wins(m.spec[u.name]))
-
-    def _dual_fwd(self, m, u, sc, x, stats_on):
-        """A downsampling block's first conv and its shortcut conv (both read the block input x)
-        in ONE launch (ops.conv_fwd_dual); False when the pair does not qualify."""
-        if not self.opts.dual_fwd or not (self._igemm_only(m, u) and self._igemm_only(m, sc)):
-            return False
-        pa, pb = m.plan[u.name, 'fwd'], m.plan[sc.name, 'fwd']
-        if tuple(pa[:2]) != tuple(pb[:2]):
-            return False
-        slab_b = m.slab
+    def _dual_fwd(self, m, s, x):
+        """A downsampling block's first conv and its shortcut conv (both read the block input
+        x) in ONE launch (ops.conv_fwd_dual); False when the launcher declines the pair."""
+        stats_on = m.train or m.group_imgs
+        pa, pb = m.plan[s.unit, 'fwd'], m.plan[s.unit2, 'fwd']
+        d = [dict(x=x, w=self.w_krsc[n], out=m.buf[n, 'y'], spec=m.spec[n],
+                  stats=m.stats[n] if stats_on else None, slab=m.slab, plan=p)
+             for n, p in ((s.unit, pa), (s.unit2, pb))]
         if pa[2] > 1 and pb[2] > 1:
-            # the shortcut's split-K partials and tile counters get a slab of their own
-            slab_b = m.buf.get((sc.name, 'slab'))
-            if slab_b is None:
-                if torch.cuda.is_current_stream_capturing():
-                    return False
-                sp = m.spec[sc.name]
-                slab_b = m.buf[sc.name, 'slab'] = torch.zeros(
-                    (slab_bytes(sp.M, sp.K, *pb[:3]) + 3) // 4, dtype=torch.float32,
-                    device=self.device)
-        a = dict(x=x, w=self.w_krsc[u.name], out=m.buf[u.name, 'y'], spec=m.spec[u.name],
-                 stats=m.stats[u.name] if stats_on else None, slab=m.slab, plan=pa)
-        b = dict(x=x, w=self.w_krsc[sc.name], out=m.buf[sc.name, 'y'], spec=m.spec[sc.name],
-                 stats=m.stats[sc.name] if stats_on else None, slab=slab_b, plan=pb)
-        return ops.conv_fwd_dual(a, b)
+            d[1]['slab'] = m.buf[s.unit2, 'slab']      # (_Mode.resolve)
+        return ops.conv_fwd_dual(*d)
 
-    def _pro_for(self, m, u, nxt):
-        """BN-apply of ``u`` folded into the load of its consumer ``nxt`` (csrc/igemm.h
-        ProParams), or None when that conv/plan cannot take it.  Train mode also keeps the
-        activation (backward reads it) through the consumer's centre-tap write-back."""
-        if not self.fuse_bn_fwd or u.act not in ('relu', 'relu6', 'none'):
-            return None
-        if nxt.depthwise:
-            # MobileNetV2's expand BN + ReLU6 applied to each chunk the depthwise conv loads
-            if not self.dw_pro:
-                return None
-            su = m.spec[u.name]
-            d = dict(dw=True, gamma=self._gamma(u), beta=self._beta(u), act=u.act, eps=BN_EPS,
-                     keep=m.buf[u.name, 'a'] if m.train else None,
-                     group_imgs=m.group_imgs or m.N)
-            if m.train or m.group_imgs:
-                d.update(stats=m.stats[u.name], count=su.group_rows or su.M)
-            else:
-                d.update(rmean=u.bn.running_mean, rvar=u.bn.running_var)
-            return d
-        pg = self._pg_pro(m, u, u.act, m.buf[u.name, 'a'] if m.train else None, nxt)
-        if pg is not None:
-            return pg
-        sp = m.spec[nxt.name]
-        if not conv_pro_ok(sp, self._pro_plan(m, nxt), keep=m.train):
-            return None
-        su = m.spec[u.name]
-        d = dict(gamma=self._gamma(u), beta=self._beta(u), act=u.act, eps=BN_EPS,
-                 keep=m.buf[u.name, 'a'] if m.train else None)
-        if m.train or m.group_imgs:
-            d.update(stats=m.stats[u.name], count=su.group_rows or su.M)
-        else:
-            d.update(rmean=u.bn.running_mean, rvar=u.bn.running_var)
-        return d
-
-    def _pg_pro(self, m, u, act, keep, nxt, res=None):
-        """Input prologue of the pointwise GEMM running ``nxt`` on the raw output of ``u``:
-        act(bn_u(y) [+ res]), activation written to ``keep`` (or None), or None when ``nxt``
-        does not run on pgemm.  Narrow-input convs whose output spans several N-tiles take the
-        panel-resident kernel instead (pwconv.hip: each element normalised once, not per tile)."""
-        if act not in ('relu', 'relu6', 'none'):
-            return None
-        su, sn = m.spec[u.name], m.spec[nxt.name]
-        if res is None and (nxt.name, 'pwconv') in m.plan and pwconv_pro_wins(sn):
-            kind = 'pw'
-        elif (nxt.name, 'pgemm') in m.plan and sn.stride == 1 and pgemm_pro_wins(sn):
-            kind = 'pg'
-        else:
-            return None
-        d = dict(gamma=self._gamma(u), beta=self._beta(u), act=act, eps=BN_EPS,
-                 keep=keep, res=res, coef=m.coef, group_rows=su.group_rows or su.M)
-        d[kind] = True
-        if m.train or m.group_imgs:
-            d.update(stats=m.stats[u.name], count=su.group_rows or su.M)
-        else:
-            d.update(rmean=u.bn.running_mean, rvar=u.bn.running_var)
-        return d
-
-    def _res_pro(self, m, u, act, out, nxt, res):
-        """Block-final BN (+ identity residual ``res``) + activation folded into the
-        register-staged load of the next block's first (pointwise) conv on igemm:
-        a = act(bn_u(y) [+ res]), the block output ``out`` written once through the prologue's
-        keep (MobileNetV2's linear-bottleneck outputs feeding the next expand conv), instead of
-        a bn_apply pass."""
-        if not self.res_pro or act not in ('relu', 'relu6', 'none') or nxt.depthwise:
-            return None
-        # (a pwconv plan only runs with its own prologue kind; with this prologue the conv runs
-        # on igemm -- not where the persistent GEMM would have run it plain, e.g. ResNet-50)
-        if any((nxt.name, k) in m.plan for k in ('stem', 'hconv')):
-            return None
-        sp = m.spec[nxt.name]
-        if (nxt.name, 'pgemm') in m.plan and pgemm_plain_wins(sp):
-            return None
-        if sp.R != 1 or not conv_pro_ok(sp, self._pro_plan(m, nxt), keep=True):
-            return None
-        su = m.spec[u.name]
-        d = dict(gamma=self._gamma(u), beta=self._beta(u), act=act, eps=BN_EPS, keep=out,
-                 res=res)
-        if m.train or m.group_imgs:
-            d.update(stats=m.stats[u.name], count=su.group_rows or su.M)
-        else:
-            d.update(rmean=u.bn.running_mean, rvar=u.bn.running_var)
-        return d
-
-    def _pool_bn(self, m, u, act):
-        d = dict(gamma=self._gamma(u), beta=self._beta(u), act=act, eps=BN_EPS)
-        if m.group_imgs:
-            d.update(stats=m.stats[u.name], group_imgs=m.group_imgs)
-        else:
-            d.update(rmean=u.bn.running_mean, rvar=u.bn.running_var)
-        return d
-
-    def _bn_apply(self, m, u, y, out, act, res=None, res_unit=None):
-        sp = m.spec[u.name]
+    def _bn_apply(self, m, s, x):
+        blk = self.lw.blocks[s.block]
+        u, sp = self.unit[s.unit], m.spec[s.unit]
+        out = m.buf[s.unit, 'a'] if s.keep == 'a' else m.buf[s.block, 'pre' if blk.pool else 'out']
+        d = self._bn_desc(m, u, s.act)
         kw = {}
-        if m.train or m.group_imgs:
-            stats, running = m.stats[u.name], None
-        else:
-            stats, running = None, (u.bn.running_mean, u.bn.running_var)
-        if res_unit is not None:
-            r2 = None if stats is not None else (res_unit.bn.running_mean,
-                                                 res_unit.bn.running_var)
-            kw['res_bn'] = (m.stats[res_unit.name] if stats is not None else None,
-                            self._gamma(res_unit), self._beta(res_unit), r2)
-        ops.bn_apply(y, stats, self._gamma(u), self._beta(u), out, sp.M, u.K,
-                     group_rows=sp.group_rows or sp.M, act=act, eps=BN_EPS, running=running,
-                     res=res, **kw)
-
-    # -- BatchNorm folded into the halo conv (csrc/hconv.hip persistent / row-step MODE 1, the
-    # scoring pass): an intra-block BN output that the next conv can stage itself stays
-    # "pending" -- (raw conv output, its BN unit, activation) -- and that conv applies it while
-    # loading its halo.  Plans: ``hconv.persist_bn_plan`` / ``m.plan[name, 'hconv_bn']``.
-    def _pending(self, u, y, act):
-        return dict(unit=u, y=y, act=act)
-
-    def _can_take(self, m, u):
-        return (u.name, 'hconv_bn') in m.plan and not u.depthwise
-
-    def _hconv_pending(self, m, u, pend, y, stats):
-        """conv ``u`` on the pending activation ``pend``: hconv with the BN applied in staging."""
-        sp = m.spec[u.name]
-        pu = pend['unit']
-        su = m.spec[pu.name]
-        pro = dict(gamma=self._gamma(pu), beta=self._beta(pu), act=pend['act'], eps=BN_EPS,
-                   count=su.group_rows or su.M, group_imgs=m.group_imgs or m.N)
-        if m.train or m.group_imgs:
-            pro['stats'] = m.stats[pu.name]
-        else:
-            pro.update(rmean=pu.bn.running_mean, rvar=pu.bn.running_var)
-        hconv.hconv_fwd(pend['y'], self.w_krsc[u.name], y, sp, m.plan[u.name, 'hconv_bn'],
-                        stats=stats, slab=m.slab,
-                        bias=self._pview(u.b_seg) if u.b_seg is not None else None, pro=pro)
+        if s.res == 'sc':
+            r = self._bn_desc(m, self.unit[s.unit2], None)
+            kw['res_bn'] = (r.get('stats'), r['gamma'], r['beta'],
+                            (r['rmean'], r['rvar']) if 'rmean' in r else None)
+        ops.bn_apply(m.buf[s.unit, 'y'], d.get('stats'), d['gamma'], d['beta'], out, sp.M, u.K,
+                     group_rows=sp.group_rows or sp.M, act=s.act, eps=BN_EPS,
+                     running=(d['rmean'], d['rvar']) if 'rmean' in d else None,
+                     res={'in': x, 'sc': m.buf.get((s.unit2, 'y')), None: None}[s.res], **kw)
 
     def forward(self, m, x=None):
-        """Forward through all blocks; returns the final activation buffer."""
-        x = m.input if x is None else x
-        stats_on = m.train or m.group_imgs
-        m.head_bn = None     # (set below when the head's pool applies the last block's BN)
-        x_last = None
-        pend = None          # an intra-block BN output the next conv applies in its staging
-        nblk = len(self.lw.blocks)
-        pool_bn = None       # BN + activation the block's max pool applies (scoring/eval stem)
-        pgp = None           # the previous block's final BN (+ identity residual), applied by the
-        #                      pointwise GEMM that consumes it (which writes the block output)
-        for bi, blk in enumerate(self.lw.blocks):
-            inp = x
-            nu = len(blk.units)
-            pro = None
-            sc_done = False      # the shortcut conv already ran (with the first conv, one launch)
-            for i, u in enumerate(blk.units):
-                y = m.buf[u.name, 'y']
-                st = m.stats[u.name] if stats_on else None
-                if pgp is not None:
-                    self._conv_fwd(m, u, pgp['y'], y, st, pro=pgp['pro'])
-                    pgp = None
-                elif (i == 0 and pend is None and blk.shortcut is not None and
-                        self._dual_fwd(m, u, blk.shortcut, inp, stats_on)):
-                    sc_done = True
-                elif pend is not None:
-                    # the previous unit's BN + act applied while staging (scoring pass: nothing
-                    # reads the intra-block activation)
-                    self._hconv_pending(m, u, pend, y, st)
-                    pend = None
-                else:
-                    self._conv_fwd(m, u, inp, y, st, pro=pro)
-                if i < nu - 1:
-                    nxt = blk.units[i + 1]
-                    if self._can_take(m, nxt) and u.act in ('relu', 'relu6', 'none'):
-                        pend = self._pending(u, y, u.act)
-                        continue
-                    # intra-block BN + activation: inside the next conv's operand load when it
-                    # can take it, else its own pass
-                    pro = self._pro_for(m, u, nxt)
-                    if pro is not None:
-                        inp = y
-                        continue
-                    a = m.buf[u.name, 'a']
-                    self._bn_apply(m, u, y, a, u.act)
-                    inp = a
-                else:
-                    out = m.buf[bi, 'pre'] if blk.pool else m.buf[bi, 'out']
-                    res, ru = None, None
-                    if blk.shortcut is not None:
-                        sc = blk.shortcut
-                        if not sc_done:
-                            self._conv_fwd(m, sc, x, m.buf[sc.name, 'y'],
-                                           m.stats[sc.name] if stats_on else None)
-                        res, ru = m.buf[sc.name, 'y'], sc
-                    elif blk.identity:
-                        res = x
-                    nb = self.lw.blocks[bi + 1] if bi + 1 < nblk else None
-                    pgd = None
-                    if nb is not None and not blk.pool and nb.units and ru is None:
-                        pgd = self._pg_pro(m, u, blk.final_act, out, nb.units[0], res=res)
-                        if pgd is None:
-                            pgd = self._res_pro(m, u, blk.final_act, out, nb.units[0], res)
-                    if pgd is not None:
-                        # the next block's first (pointwise) conv applies this BN (+ identity
-                        # residual) + activation in its operand tiles and writes ``out``
-                        pgp = dict(y=y, pro=pgd)
-                    elif (nb is None and not m.train and not blk.pool and ru is None and
-                          self.opts.head_bn and self.lw.head_pool != 'mlp2' and
-                          blk.final_act in ('relu', 'relu6', 'none') and u.K % 8 == 0):
-                        # scoring / eval: nothing reads the last block's output but the head's
-                        # average pool, which applies this BN (+ identity residual) +
-                        # activation itself (ops.head_fwd ``bn``): no bn_apply pass
-                        hb = dict(gamma=self._gamma(u), beta=self._beta(u), act=blk.final_act,
-                                  eps=BN_EPS, res=res)
-                        if m.group_imgs:
-                            su = m.spec[u.name]
-                            hb.update(stats=m.stats[u.name], count=su.group_rows or su.M,
-                                      group_imgs=m.group_imgs)
-                        else:
-                            hb.update(rmean=u.bn.running_mean, rvar=u.bn.running_var)
-                        m.head_bn = hb
-                        x_last = y
-                    elif (blk.pool and not m.train and res is None and
-                          blk.final_act in ('relu', 'relu6', 'none')):
-                        # scoring / eval (nothing reads the pre-pool activation): the pool
-                        # applies this BN + activation per tap, straight from the conv output
-                        pool_bn = self._pool_bn(m, u, blk.final_act)
-                    else:
-                        self._bn_apply(m, u, y, out, blk.final_act, res=res, res_unit=ru)
-            if blk.pool:
-                N, h, w, K, P_, Q_, k, st, pd = m.buf[bi, 'pool_geom']
-                src = m.buf[bi, 'pre']
-                if pool_bn is not None:
-                    src = m.buf[blk.units[-1].name, 'y']
-                ops.pool2d_fwd(src, m.buf[bi, 'out'], N, h, w, K, P_, Q_, k, st, pd,
-                               True, m.buf.get((bi, 'argmax')), bn=pool_bn)
-                pool_bn = None
-            x = m.buf[bi, 'out']
-        if m.head_bn is not None:
-            return x_last            # the raw last conv output: the head applies its BN
-        return x
+        """Forward through all blocks: walks ``m.fwd_steps`` (schedule.forward_schedule).
+        Returns the final activation buffer, or the raw last conv output when the head applies
+        the last block's BN (``m.head_bn``)."""
+        x0 = m.input if x is None else x
+        m.head_bn = None
+        late_sc = None       # a shortcut conv whose dual launch was declined
+        for s in m.fwd_steps:
+            x = self._block_in(m, s.block, x0)
+            src = x if s.src == 'in' else m.buf[{'pre': (s.block, 'pre'), 'act': (s.src_unit, 'a'),
+                                                 'raw': (s.src_unit, 'y')}[s.src]]
+            if s.op == 'conv':
+                self._conv_fwd(m, s.unit, s.route, src, self._pro(m, s, x0))
+            elif s.op == 'dual_conv':
+                if not self._dual_fwd(m, s, x):
+                    self._conv_fwd(m, s.unit, 'igemm', x)
+                    late_sc = s.unit2
+            elif s.op == 'bn_apply':
+                if s.res == 'sc' and late_sc is not None:
+                    self._conv_fwd(m, late_sc, 'igemm', x)
+                    late_sc = None
+                self._bn_apply(m, s, x)
+            elif s.op == 'pool':
+                N, h, w, K, P_, Q_, k, st, pd = m.buf[s.block, 'pool_geom']
+                bn = self._bn_desc(m, self.unit[s.unit], s.act, count=False, ghost=True) \
+                    if s.pro else None
+                ops.pool2d_fwd(src, m.buf[s.block, 'out'], N, h, w, K, P_, Q_, k, st, pd,
+                               True, m.buf.get((s.block, 'argmax')), bn=bn)
+            else:
+                # scoring / eval: the head's average pool applies the last block's BN (+
+                # identity residual) + activation itself (ops.head_fwd ``bn``)
+                m.head_bn = self._bn_desc(m, self.unit[s.unit], s.act, ghost=True,
+                                          res=x if s.res == 'in' else None)
+                return src
+        return m.buf[len(self.lw.blocks) - 1, 'out']
 
     # ------------------------------------------------------------------ speech-VGG head
     # flatten -> fc1 -> fc2 -> log_softmax (CE on log-probs == CE on logits), all HIP kernels
@@ -894,96 +656,60 @@ class NativeEngine(object):
     def _wgrad(self, m, u, dy, x):
         sp = m.spec[u.name]
         gw = self._pview(u.w_seg, grad=True)
-        if u.depthwise:
-            if m.dw_slab is not None:
-                off, n, _ = m.dw_region[u.name]
-                ops.dwconv_wgrad(dy, x, gw, sp.N, sp.H, sp.W, sp.C, sp.P, sp.Q, sp.stride,
-                                 sp.pad, slab=m.dw_slab[off:off + n])
-            else:
-                ops.dwconv_wgrad(dy, x, gw, sp.N, sp.H, sp.W, sp.C, sp.P, sp.Q, sp.stride,
-                                 sp.pad)
+        if u.depthwise:          # (a train mode with a depthwise unit has its dw_slab region)
+            off, n, _ = m.dw_region[u.name]
+            ops.dwconv_wgrad(dy, x, gw, sp.N, sp.H, sp.W, sp.C, sp.P, sp.Q, sp.stride,
+                             sp.pad, slab=m.dw_slab[off:off + n])
         else:
             ops.conv_wgrad(dy, x, gw, sp, plan=m.plan[u.name, 'wgrad'])
 
-    def _conv_bwd(self, m, u, dy, x, dx, accumulate, bw=None):
-        """Weight gradient, then the data gradient.  ``bw``: the dgrad epilogue also reduces
-        the BN-backward sums of the unit feeding ``dx`` (returns True when it did, so the
-        caller skips bn_bwd's reduce pass)."""
-        sp = m.spec[u.name]
-        if (dx is not None and not u.depthwise and self.pair_bwd and sp.K % 8 == 0):
-            if bw is not None and (sp.Cp != sp.C or not self.fuse_bn_bwd):
-                bw = None
+    def _conv_bwd(self, m, name, kind, dy, x, dx, accumulate=False, bw=None):
+        """Weight gradient and (``dx``) data gradient of conv ``name`` by launch ``kind``
+        (schedule.BwdStep).  ``bw``: the dgrad epilogue also reduces the BN-backward sums of
+        the unit feeding ``dx``."""
+        u, sp = self.unit[name], m.spec[name]
+        if kind == 'pair':
             # dgrad + wgrad of this conv in ONE launch (they share dy and are independent)
-            ops.conv_bwd(dy, self.w_crsk[u.name], dx, x, self._pview(u.w_seg, grad=True), sp,
-                         dplan=m.plan[u.name, 'dgrad'], wplan=m.plan[u.name, 'wgrad'],
+            ops.conv_bwd(dy, self.w_crsk[name], dx, x, self._pview(u.w_seg, grad=True), sp,
+                         dplan=m.plan[name, 'dgrad'], wplan=m.plan[name, 'wgrad'],
                          slab=m.slab, accumulate=accumulate, bw=bw)
-            return bw is not None
-        if u.depthwise and dx is not None and m.dw_slab is not None and self.dw_pair:
+        elif kind == 'dw_pair':
             assert not accumulate
-            # the producer's BN-backward sums reduced in the depthwise dgrad (no bn_bwd reduce
-            # pass; one batch group in train mode, no shortcut BN)
-            if bw is not None and (not self.fuse_bn_bwd or bw.get('y2') is not None):
-                bw = None
             # dgrad + wgrad in one launch; the wgrad partials' reduce is deferred to one batched
-            # launch (flush_dw_reduces) -- nothing reads a depthwise weight gradient before the
-            # optimizer or its bucket's all-reduce
-            off, n, nblk = m.dw_region[u.name]
+            # launch (flush_dw_reduces): at the end of the backward, or (DP) before the bucket
+            # all-reduce that carries this weight gradient (train_segments) -- nothing reads a
+            # depthwise weight gradient before the optimizer or its bucket's all-reduce
+            off, n, nblk = m.dw_region[name]
             region = m.dw_slab[off:off + n]
             gw = self._pview(u.w_seg, grad=True)
-            # deferred to one batched launch: at the end of the backward, or (DP) before the
-            # bucket all-reduce that carries this weight gradient (train_segments)
-            defer = True
             ops.dwconv_bwd(dy, x, self._pview(u.w_seg), dx, gw, sp.N, sp.H, sp.W, sp.C, sp.P,
-                           sp.Q, sp.stride, sp.pad, region, bw=bw, reduce=not defer)
-            if defer:
-                m.dw_pending.append((region, gw, sp.C, nblk))
-            return bw is not None
-        self._wgrad(m, u, dy, x)
-        if u.depthwise:
-            if dx is None:
-                return False
-            assert not accumulate
-            if bw is not None and (not self.fuse_bn_bwd or bw.get('y2') is not None):
-                bw = None
-            ops.dwconv_dgrad(dy, self._pview(u.w_seg), dx, sp.N, sp.H, sp.W, sp.C, sp.P,
-                             sp.Q, sp.stride, sp.pad, bw=bw)
-            return bw is not None
-        if dx is not None:
-            if bw is not None and (sp.Cp != sp.C or not self.fuse_bn_bwd):
-                bw = None
-            ops.conv_dgrad(dy, self.w_crsk[u.name], dx, sp, slab=m.slab,
-                           plan=m.plan[u.name, 'dgrad'], accumulate=accumulate, bw=bw)
-            return bw is not None
-        return False
+                           sp.Q, sp.stride, sp.pad, region, bw=bw, reduce=False)
+            m.dw_pending.append((region, gw, sp.C, nblk))
+        else:
+            self._wgrad(m, u, dy, x)
+            if dx is not None and u.depthwise:
+                assert not accumulate
+                ops.dwconv_dgrad(dy, self._pview(u.w_seg), dx, sp.N, sp.H, sp.W, sp.C, sp.P,
+                                 sp.Q, sp.stride, sp.pad, bw=bw)
+            elif dx is not None:
+                ops.conv_dgrad(dy, self.w_crsk[name], dx, sp, slab=m.slab,
+                               plan=m.plan[name, 'dgrad'], accumulate=accumulate, bw=bw)
 
-    def _bwd_sc_ok(self, m, u, sc):
-        """Can the shortcut ``sc``'s backward share one launch with ``u``'s (ops.conv_bwd_sc)?"""
-        if not self.opts.dual_bwd or not self.pair_bwd or u.depthwise or sc.depthwise:
-            return False
-        su, ss = m.spec[u.name], m.spec[sc.name]
-        if su.stride != 1 or su.K % 8 or ss.K % 8 or not ops.conv.dgrad_s2_ok(ss) or ss.N > 32:
-            return False
-        return (tuple(m.plan[u.name, 'dgrad'][:2]) == (64, 64) and
-                tuple(m.plan[u.name, 'wgrad'][:2]) in ((64, 64), (128, 128)) and
-                tuple(m.plan[sc.name, 'wgrad'][:2]) == (64, 64))
-
-    def _conv_bwd_sc(self, m, u, dy, x, dx, bw, sc, xs, dxs):
-        """``u``'s dgrad + wgrad (dx, fused BN-backward sums ``bw``) and the shortcut ``sc``'s
-        (input ``xs``, writes ``dxs``) in one launch; two launches when the pair does not fit.
-        Returns whether ``bw`` was reduced (as _conv_bwd)."""
-        sp = m.spec[u.name]
-        if bw is not None and (sp.Cp != sp.C or not self.fuse_bn_bwd):
-            bw = None
+    def _conv_bwd_sc(self, m, s, dy, x, dx, bw, xs, dxs):
+        """``s.unit``'s dgrad + wgrad (dx, fused BN-backward sums ``bw``) and the shortcut
+        ``s.unit2``'s (input ``xs``, writes ``dxs``) in one launch; two launches when the
+        launcher declines the pair."""
+        u, sc = self.unit[s.unit], self.unit[s.unit2]
         a = dict(dy=dy, wt=self.w_crsk[u.name], dx=dx, x=x, dw=self._pview(u.w_seg, grad=True),
-                 spec=sp, dplan=m.plan[u.name, 'dgrad'], wplan=m.plan[u.name, 'wgrad'],
-                 slab=m.slab, accumulate=False, bw=bw)
+                 spec=m.spec[u.name], dplan=m.plan[u.name, 'dgrad'],
+                 wplan=m.plan[u.name, 'wgrad'], slab=m.slab, accumulate=False, bw=bw)
         b = dict(dy=m.buf[sc.name, 'dy'], wt=self.w_crsk[sc.name], dx=dxs, x=xs,
                  dw=self._pview(sc.w_seg, grad=True), spec=m.spec[sc.name],
                  wplan=m.plan[sc.name, 'wgrad'], accumulate=False)
         if ops.conv.conv_bwd_sc(a, b):
-            return bw is not None
-        self._conv_bwd(m, sc, m.buf[sc.name, 'dy'], xs, dxs, accumulate=False)
-        return self._conv_bwd(m, u, dy, x, dx, accumulate=False, bw=bw)
+            return
+        self._conv_bwd(m, sc.name, 'pair', m.buf[sc.name, 'dy'], xs, dxs)
+        self._conv_bwd(m, u.name, 'pair', dy, x, dx, bw=bw)
 
     def _bw(self, m, u, out, act, unit2=None):
         """Fused-reduce descriptor for the BN of ``u`` (+ shortcut BN ``unit2``) whose activation
@@ -1012,73 +738,53 @@ class NativeEngine(object):
         if bi == 0:                      # the backward is complete: deferred reduces
             self.flush_dw_reduces(m)
 
+    def _bwd_step(self, m, s):
+        """One launch of the backward schedule (schedule.BwdStep)."""
+        bi, blk = s.block, self.lw.blocks[s.block]
+        x = m.buf[bi - 1, 'out'] if bi > 0 else m.input
+        dx = m.buf.get((bi - 1, 'dout'))
+        u = self.unit[s.unit]
+        final = u is blk.units[-1]
+        pre = 'pre' if blk.pool else 'out'
+        if s.op == 'pool_bwd':
+            N, h, w, K, P_, Q_, k, st, pd = m.buf[bi, 'pool_geom']
+            ops.maxpool2d_bwd(m.buf[bi, 'dout'], m.buf[bi, 'argmax'], m.buf[bi, 'dpre'], N, h, w,
+                              K, P_, Q_, k, st, pd)
+        elif s.op == 'bn_bwd' and final:
+            sc = blk.shortcut
+            reduce = s.reduce == 'pass' or (s.reduce == 'head' and not m.head_reduced)
+            m.head_reduced = False
+            self._bn_bwd(m, u, m.buf[bi, 'd' + pre], m.buf[bi, pre], blk.final_act,
+                         m.buf[u.name, 'dy'], unit2=sc, dy2=m.buf[sc.name, 'dy'] if sc else None,
+                         dz=dx if s.dx else None, reduce=reduce)
+        elif s.op == 'bn_bwd':
+            self._bn_bwd(m, u, m.buf[u.name, 'da'], m.buf[u.name, 'a'], u.act,
+                         m.buf[u.name, 'dy'], reduce=s.reduce == 'pass')
+        else:
+            i = blk.units.index(u) if u is not blk.shortcut else 0
+            inp = x if i == 0 else m.buf[blk.units[i - 1].name, 'a']
+            bw = None
+            if s.bw is not None and i > 0:
+                p = blk.units[i - 1]
+                bw = self._bw(m, p, m.buf[p.name, 'a'], p.act)
+            elif s.bw is not None:
+                pb = self.lw.blocks[bi - 1]
+                bw = self._bw(m, pb.units[-1], m.buf[bi - 1, 'out'], pb.final_act,
+                              unit2=pb.shortcut)
+            d = {'block': dx, 'da': m.buf.get((blk.units[i - 1].name, 'da')), None: None}[s.dx]
+            if s.kind == 'pair_sc':
+                self._conv_bwd_sc(m, s, m.buf[u.name, 'dy'], inp, d, bw, x, dx)
+            else:
+                self._conv_bwd(m, u.name, s.kind, m.buf[u.name, 'dy'], inp, d,
+                               accumulate=s.acc, bw=bw)
+
     def backward_parts(self, m, bi):
         """Block ``bi``'s backward as [(unit index, callable)] in execution order (last unit
         first): after part i, the gradients of units i..last, of the BNs of units i-1..last
         and of the shortcut are final -- so a gradient bucket may close between parts."""
-        blk = self.lw.blocks[bi]
-        x = m.buf[bi - 1, 'out'] if bi > 0 else m.input
-        dx = m.buf[bi - 1, 'dout'] if (bi > 0 and blk.need_dx) else None
-        units = blk.units
-        last = units[-1]
-        sc = blk.shortcut
+        return [(i, lambda steps=steps: [self._bwd_step(m, s) for s in steps])
+                for i, steps in m.bwd.parts[bi]]
 
-        # the shortcut's backward runs in ONE launch with the last conv's (both start from the
-        # block-final BN's backward; EngineOptions.dual_bwd)
-        merge = (sc is not None and dx is not None and len(units) > 1 and
-                 self._bwd_sc_ok(m, last, sc))
-
-        def top():
-            dout = m.buf[bi, 'dout']
-            out = m.buf[bi, 'out']
-            if blk.pool:
-                N, h, w, K, P_, Q_, k, st, pd = m.buf[bi, 'pool_geom']
-                ops.maxpool2d_bwd(dout, m.buf[bi, 'argmax'], m.buf[bi, 'dpre'], N, h, w, K, P_,
-                                  Q_, k, st, pd)
-                dout, out = m.buf[bi, 'dpre'], m.buf[bi, 'pre']
-            dz = dx if (blk.identity and dx is not None) else None
-            pre = m.prereduced.pop(bi, False) and not blk.pool
-            self._bn_bwd(m, last, dout, out, blk.final_act, m.buf[last.name, 'dy'], unit2=sc,
-                         dy2=m.buf[sc.name, 'dy'] if sc else None, dz=dz, reduce=not pre)
-            if sc is not None and not merge:
-                self._conv_bwd(m, sc, m.buf[sc.name, 'dy'], x, dx, accumulate=False)
-
-        def unit(i):
-            u = units[i]
-            d = m.buf[u.name, 'dy']
-            inp = x if i == 0 else m.buf[units[i - 1].name, 'a']
-            if i > 0:
-                prev = units[i - 1]
-                da = m.buf[prev.name, 'da']
-                bw = self._bw(m, prev, m.buf[prev.name, 'a'], prev.act)
-                if merge and u is last:
-                    fused = self._conv_bwd_sc(m, u, d, inp, da, bw, sc, x, dx)
-                else:
-                    fused = self._conv_bwd(m, u, d, inp, da, accumulate=False, bw=bw)
-                self._bn_bwd(m, prev, da, m.buf[prev.name, 'a'], prev.act,
-                             m.buf[prev.name, 'dy'], reduce=not fused)
-            else:
-                acc = blk.identity or sc is not None
-                bw = None
-                if bi > 0 and dx is not None:
-                    # this dgrad is the LAST writer of the previous block's output gradient:
-                    # reduce that block's final BN (+ shortcut BN) sums in its epilogue
-                    pb = self.lw.blocks[bi - 1]
-                    if not pb.pool:
-                        bw = self._bw(m, pb.units[-1], m.buf[bi - 1, 'out'], pb.final_act,
-                                      unit2=pb.shortcut)
-                fused = self._conv_bwd(m, u, d, inp, dx if u.need_dgrad else None,
-                                       accumulate=acc, bw=bw)
-                if fused:
-                    m.prereduced[bi - 1] = True
-
-        parts = []
-        for i in range(len(units) - 1, -1, -1):
-            if i == len(units) - 1:
-                parts.append((i, lambda i=i: (top(), unit(i))))
-            else:
-                parts.append((i, lambda i=i: unit(i)))
-        return parts
 
     # ------------------------------------------------------------------ data
     def _device_inputs(self, images):
@@ -1255,14 +961,13 @@ class NativeEngine(object):
             # pass at the top of the last block) where its per-sample path runs
             lb = self.lw.blocks[last]
             bw = None
-            if self.head_bw and self.fuse_bn_bwd and not lb.pool:
+            if tm.bwd.head_bw:
                 bw = self._bw(tm, lb.units[-1], tm.buf[last, 'out'], lb.final_act,
                               unit2=lb.shortcut)
-            if ops.head_bwd(tm.pooled, tm.dlogits, self._pview(self.lw.fc_w),
-                            self._pview(self.lw.fc_w, True), self._pview(self.lw.fc_b, True),
-                            tm.buf[last, 'dout'], self.B, tm.final_hw, tm.final_C,
-                            self.classes, bw=bw):
-                tm.prereduced[last] = True
+            tm.head_reduced = bool(ops.head_bwd(
+                tm.pooled, tm.dlogits, self._pview(self.lw.fc_w), self._pview(self.lw.fc_w, True),
+                self._pview(self.lw.fc_b, True), tm.buf[last, 'dout'], self.B, tm.final_hw,
+                tm.final_C, self.classes, bw=bw))
         cuts = self.bucket_plan()
         dw = any(u.depthwise for u in self.units)
         cur = [fwd_head]
@@ -1398,6 +1103,8 @@ class NativeEngine(object):
 
     def _build_graphs(self):
         self._apply_globals()
+        for m in self.modes.values():
+            m.resolve()                  # (the plans may have changed: ops/step_tune.py)
         cap = torch.cuda.Stream(self.device)
         segs = self.train_segments()
         comm_ev = (self.dp and self.s_comm is not None

@@ -75,13 +75,18 @@ _CFG = dict(persist=True, plans='', waves=8, grid=0, row='score', wm8=0, swa=Tru
 
 
 def configure(opts):
-    """Take the halo-kernel switches of an ``EngineOptions`` (the persistent kernel's grid and
-    wave count are also handed to the C++ launcher)."""
+    """Take the halo-kernel switches of an ``EngineOptions`` (Python side only: plan building
+    reads them; ``configure_launcher`` hands the C++ launcher its share)."""
     _CFG.update(persist=bool(opts.hconv_persist), plans=opts.hconv_plans or '',
                 waves=8 if opts.hconv_persist_waves == 8 else 4,
                 grid=int(opts.hconv_persist_grid), row=opts.hconv_row,
                 wm8=int(opts.hconv_persist_wm8), swa=bool(opts.hconv_swa),
                 pad=bool(opts.hconv_pad))
+
+
+def configure_launcher():
+    """The persistent kernel's grid and wave count of the last ``configure``, to the C++
+    launcher."""
     lib().hconv_configure(_CFG['grid'], _CFG['waves'], _CFG['wm8'])
 
 

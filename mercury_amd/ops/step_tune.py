@@ -86,6 +86,7 @@ def _set(kind, users, plan):
             m.plan[name, 'dgrad'] = tuple(d)
             m.plan[name, 'wgrad'] = tuple(w)
             _ensure_slab(m, slab_bytes(sp.N * sp.H * sp.W, sp.Cp, *d))
+        m.resolve()                      # the launch schedules depend on the plans
 
 
 def _candidates(kind, sp, cur, max_split):

@@ -357,3 +357,110 @@ def test_head_applies_final_bn_in_pool(arch):
     assert torch.isfinite(l1).all()
     assert float((l1 - l0).abs().mean()) < 2e-2 * max(1.0, float(l0.abs().mean()))
     assert abs(e1[0] - e0[0]) < 2e-2 * max(1.0, abs(e0[0])) and e1[2] == e0[2] == 64
+
+
+def _record_launches(monkeypatch, m, log):
+    """Wrap the ops entry points the engine's walkers call: each call appends what ran and on
+    which unit (found by its output / gradient buffer in mode ``m``) to ``log``."""
+    from mercury_amd import ops
+    from mercury_amd.ops import conv, hconv
+    names = lambda role: {t.data_ptr(): k[0] for k, t in m.buf.items()  # noqa: E731
+                          if k[1] == role and torch.is_tensor(t)}
+    y, dy, out, dout = names('y'), names('dy'), names('out'), names('dout')
+
+    def wrap(mod, fn, entry):
+        f = getattr(mod, fn)
+
+        def g(*a, **kw):
+            r = f(*a, **kw)
+            e = entry(a, kw, r)
+            if e is not None:
+                log.append(e)
+            return r
+        monkeypatch.setattr(mod, fn, g)
+
+    for fn, route in (('conv_fwd', 'igemm'), ('pgemm_fwd', 'pgemm'), ('pwconv_fwd', 'pwconv'),
+                      ('stem_fwd', 'stem'), ('dwconv_fwd', 'dwconv')):
+        wrap(ops, fn, lambda a, kw, r, route=route: ('conv', route, y[a[2].data_ptr()]))
+    wrap(hconv, 'hconv_fwd', lambda a, kw, r: ('conv', 'hconv', y[a[2].data_ptr()]))
+    wrap(ops, 'conv_fwd_dual', lambda a, kw, r: ('dual_conv', y[a[0]['out'].data_ptr()],
+                                                 y[a[1]['out'].data_ptr()], bool(r)))
+    wrap(ops, 'bn_apply', lambda a, kw, r: ('bn_apply', y[a[0].data_ptr()]))
+    wrap(ops, 'pool2d_fwd', lambda a, kw, r: ('pool', out[a[1].data_ptr()],
+                                              kw.get('bn') is not None))
+    wrap(ops, 'head_fwd', lambda a, kw, r: ('head_bn',) if kw.get('bn') is not None else None)
+    bw = lambda kw: kw.get('bw') is not None  # noqa: E731
+    for fn in ('conv_bwd', 'conv_dgrad', 'conv_wgrad', 'dwconv_bwd', 'dwconv_dgrad',
+               'dwconv_wgrad'):
+        wrap(ops, fn, lambda a, kw, r, fn=fn: (fn, dy[a[0].data_ptr()], bw(kw)))
+    wrap(conv, 'conv_bwd_sc', lambda a, kw, r: ('conv_bwd_sc', dy[a[0]['dy'].data_ptr()],
+                                                dy[a[1]['dy'].data_ptr()], bw(a[0]), bool(r)))
+    wrap(ops, 'bn_bwd', lambda a, kw, r: ('bn_bwd', y[a[2].data_ptr()], kw['reduce']))
+    wrap(ops, 'maxpool2d_bwd', lambda a, kw, r: ('pool_bwd', dout[a[0].data_ptr()]))
+    wrap(ops, 'head_bwd', lambda a, kw, r: ('head_bwd', bw(kw), bool(r)))
+
+
+def _fwd_expected(m):
+    e = []
+    for s in m.fwd_steps:
+        if s.op == 'conv':
+            e.append(('conv', s.route, s.unit))
+        elif s.op == 'dual_conv':
+            e.append(('dual_conv', s.unit, s.unit2, True))
+        elif s.op == 'pool':
+            e.append(('pool', s.block, s.pro == 'pool'))
+        else:
+            e.append((s.op, s.unit) if s.op == 'bn_apply' else ('head_bn',))
+    return e
+
+
+def _bwd_expected(eng, m, head_reduced):
+    e = []
+    for bi in range(len(eng.lw.blocks) - 1, -1, -1):
+        for _, steps in m.bwd.parts[bi]:
+            for s in steps:
+                dwc = eng.unit[s.unit].depthwise
+                if s.op == 'pool_bwd':
+                    e.append(('pool_bwd', bi))
+                elif s.op == 'bn_bwd':
+                    e.append(('bn_bwd', s.unit, s.reduce == 'pass' or
+                              (s.reduce == 'head' and not head_reduced)))
+                elif s.kind == 'pair_sc':
+                    e.append(('conv_bwd_sc', s.unit, s.unit2, s.bw is not None, True))
+                elif s.kind in ('pair', 'dw_pair'):
+                    e.append(('conv_bwd' if s.kind == 'pair' else 'dwconv_bwd', s.unit,
+                              s.bw is not None))
+                else:
+                    e.append(('dwconv_wgrad' if dwc else 'conv_wgrad', s.unit, False))
+                    if s.dx is not None:
+                        e.append(('dwconv_dgrad' if dwc else 'conv_dgrad', s.unit,
+                                  s.bw is not None))
+    return e
+
+
+@pytest.mark.parametrize('arch', ['resnet18', 'mobilenetv2'])
+def test_engine_runs_its_schedule(arch, monkeypatch):
+    """What ``forward`` and ``backward_parts`` launch is ``m.fwd_steps`` / ``m.bwd`` step for
+    step (scoring mode: pool 320 in ghost-BN groups of 32; train mode: batch 32): the schedule
+    is the description of what runs, not a second one that can drift."""
+    from mercury_amd.models import build_model
+    torch.manual_seed(4)
+    eng = _engine(build_model(arch, 100 if arch == 'mobilenetv2' else 10).to(DEV))
+    sm, tm = eng.score_mode, eng.train_mode
+    log = []
+    _record_launches(monkeypatch, sm, log)
+    eng.prime()                          # the scoring forward, eagerly
+    assert log == _fwd_expected(sm)
+    monkeypatch.undo()
+    del log[:]
+    _record_launches(monkeypatch, tm, log)
+    for fs, _ in eng.train_segments():   # train forward, head, backward
+        for f in fs:
+            f()
+    torch.cuda.synchronize()
+    nf = len(tm.fwd_steps)
+    assert log[:nf] == _fwd_expected(tm)
+    assert log[nf] == ('head_bwd', tm.bwd.head_bw, log[nf][2])
+    assert log[nf + 1:] == _bwd_expected(eng, tm, head_reduced=log[nf][2])
+    assert math.isfinite(eng.meters[0].item())
+    eng.close()
