@@ -542,6 +542,32 @@ PYBIND11_MODULE(_C, m) {
     pool_build_launch(a, S(st));
     check_launch("pool_build");
   });
+  m.def("pool_augment", [](uintptr_t shard, uintptr_t labels, uintptr_t ctrl, uintptr_t pool,
+                           uintptr_t pool_label, uintptr_t pool_index, int Ns, int Hs, int Ws,
+                           int H, int W, int Pn, int batch, int pad, int flip, int augment,
+                           int shuffle, uint32_t seed, std::vector<float> mean,
+                           std::vector<float> inv_std, uintptr_t st, uintptr_t zero, int nzero,
+                           int resize, int Hr, int Wr, float degrees, float scale_lo,
+                           float scale_hi, int cutout, int affine, uintptr_t params) {
+    if (Ns < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || Pn < 1 || batch < 1 || pad < 0)
+      throw std::runtime_error("pool_augment: sizes must be positive");
+    if (resize ? (Hr < 1 || Wr < 1) : (Hr != Hs || Wr != Ws))
+      throw std::runtime_error("pool_augment: resized size does not match the recipe");
+    if (Hr + 2 * pad < H || Wr + 2 * pad < W)
+      throw std::runtime_error("pool_augment: empty crop range (crop larger than the padded image)");
+    if (degrees < 0.f || !(scale_lo > 0.f) || scale_hi < scale_lo || cutout < 0)
+      throw std::runtime_error("pool_augment: degrees >= 0, 0 < scale_lo <= scale_hi, cutout >= 0");
+    if (mean.size() != 3 || inv_std.size() != 3)
+      throw std::runtime_error("pool_augment: mean and std have three channels");
+    PoolAugmentArgs a{{P<const uint8_t>(shard), P<const int64_t>(labels), P<const int64_t>(ctrl),
+                       P<bf16>(pool), P<int>(pool_label), P<int>(pool_index), Ns, H, W, Pn, batch,
+                       pad, flip, augment, shuffle, seed, {mean[0], mean[1], mean[2]},
+                       {inv_std[0], inv_std[1], inv_std[2]}, 0, P<float>(zero), nzero},
+                      Hs, Ws, resize, Hr, Wr, degrees, scale_lo, scale_hi, cutout, affine,
+                      P<float>(params)};
+    pool_augment_launch(a, S(st));
+    check_launch("pool_augment");
+  });
   m.def("is_sample", [](uintptr_t losses, uintptr_t ema, uintptr_t ctrl, uintptr_t idx, uintptr_t w,
                         uintptr_t meters, int Pn, int B, int group, int importance, float alpha,
                         float ema_alpha, uint32_t seed, uintptr_t st, int alias, uintptr_t gl,

@@ -97,6 +97,133 @@ __global__ __launch_bounds__(256) void pool_build_kernel(PoolBuildArgs a) {
   }
 }
 
+// ---- augmentation recipes (PoolAugmentArgs) ------------------------------------------------
+// Tap (y, x) of the cropped view, 0 <= y < H, 0 <= x < W: undo the flip, move into the padded
+// resized image, zero in the padding; the resized image itself is torch's bilinear with
+// align_corners=False over the uint8 source, every source index clamped into the image.
+template <bool RESIZE>
+MA_DEV void aug_tap(const PoolAugmentArgs& a, const uint8_t* img, int y, int x, int dy, int dx,
+                    int flip, float ry, float rx, float v[3]) {
+  const int xc = flip ? (a.b.W - 1 - x) : x;
+  const int ys = y + dy - a.b.pad, xs = xc + dx - a.b.pad;
+  v[0] = v[1] = v[2] = 0.f;
+  if (ys < 0 || xs < 0 || ys >= a.Hr || xs >= a.Wr) return;
+  if (!RESIZE) {               // (Hr, Wr) == (Hs, Ws), checked by the binding
+    const uint8_t* p = img + ((size_t)ys * a.Ws + xs) * 3;
+    v[0] = p[0];
+    v[1] = p[1];
+    v[2] = p[2];
+    return;
+  }
+  const float fy = fmaxf((ys + 0.5f) * ry - 0.5f, 0.f), fx = fmaxf((xs + 0.5f) * rx - 0.5f, 0.f);
+  const int y0 = min((int)fy, a.Hs - 1), x0 = min((int)fx, a.Ws - 1);
+  const int y1 = min(y0 + 1, a.Hs - 1), x1 = min(x0 + 1, a.Ws - 1);
+  const float ly = fy - y0, lx = fx - x0;
+  const uint8_t* p0 = img + (size_t)y0 * a.Ws * 3;
+  const uint8_t* p1 = img + (size_t)y1 * a.Ws * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float top = p0[x0 * 3 + c] * (1.f - lx) + p0[x1 * 3 + c] * lx;
+    const float bot = p1[x0 * 3 + c] * (1.f - lx) + p1[x1 * 3 + c] * lx;
+    v[c] = top * (1.f - ly) + bot * ly;
+  }
+}
+
+// One block per pool slot, like pool_build_kernel, whose crop / flip draw (first Philox call)
+// this repeats word for word: a crop-and-flip recipe on a shard of the output size gives the
+// same bits from either kernel.
+template <bool AFFINE, bool RESIZE>
+__global__ __launch_bounds__(256) void pool_augment_kernel(PoolAugmentArgs a) {
+  const PoolBuildArgs& b = a.b;
+  const int slot = blockIdx.x;
+  if (b.zero) zero_slice(b);
+  int64_t gb;
+  int t;
+  const uint32_t src = pool_src(b, slot, gb, t);
+  const int H = b.H, W = b.W;
+  int dy = (a.Hr + 2 * b.pad - H) / 2, dx = (a.Wr + 2 * b.pad - W) / 2, flip = 0;
+  float angle = 0.f, scale = 1.f;
+  int cut_y = 0, cut_x = 0, cut = 0;
+  if (b.augment) {
+    const u32x4 r = philox4x32(u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5eedu},
+                               b.seed, 0xA5A5A5A5u);
+    dy = r.x % (a.Hr + 2 * b.pad - H + 1);
+    dx = r.y % (a.Wr + 2 * b.pad - W + 1);
+    flip = b.flip ? (r.z & 1) : 0;
+    const u32x4 q = philox4x32(u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5eeeu},
+                               b.seed, 0xA5A5A5A5u);
+    angle = -a.degrees + 2.f * a.degrees * u01(q.x);
+    scale = a.scale_lo + (a.scale_hi - a.scale_lo) * u01(q.y);
+    cut_y = q.z % H;
+    cut_x = q.w % W;
+    cut = a.cutout;
+  }
+  if (threadIdx.x == 0) {
+    b.pool_label[slot] = (int)b.labels[src];
+    b.pool_index[slot] = (int)src;
+    if (a.params) {
+      float* p = a.params + (size_t)slot * 8;
+      p[0] = (float)dy;
+      p[1] = (float)dx;
+      p[2] = (float)flip;
+      p[3] = angle;
+      p[4] = scale;
+      p[5] = (float)cut_y;
+      p[6] = (float)cut_x;
+      p[7] = 0.f;
+    }
+  }
+  // Cutout.__call__: [clip(c - L/2, 0, n), clip(c + L/2, 0, n)) in both axes (empty when off)
+  const int ch = cut / 2;
+  const int cy0 = cut ? max(cut_y - ch, 0) : 0, cy1 = cut ? min(cut_y + ch, H) : 0;
+  const int cx0 = cut ? max(cut_x - ch, 0) : 0, cx1 = cut ? min(cut_x + ch, W) : 0;
+  const float ry = (float)a.Hs / (float)a.Hr, rx = (float)a.Ws / (float)a.Wr;
+  float cs = 1.f, sn = 0.f;
+  if (AFFINE) {
+    const float rad = angle * 0.017453292519943295f;
+    cs = cosf(rad) / scale;
+    sn = sinf(rad) / scale;
+  }
+  const uint8_t* img = b.shard + (size_t)src * a.Hs * a.Ws * 3;
+  bf16* out = b.pool + (size_t)slot * H * W * 8;
+  const int npx = H * W;
+  for (int px = threadIdx.x; px < npx; px += 256) {
+    const int i = px / W, j = px - i * W;
+    float v[3];
+    if (AFFINE) {
+      // affine_grid + grid_sample (bilinear, zeros padding, align_corners=False)
+      const float xn = (2 * j + 1) / (float)W - 1.f, yn = (2 * i + 1) / (float)H - 1.f;
+      const float gx = cs * xn - sn * yn, gy = sn * xn + cs * yn;
+      const float fx = ((gx + 1.f) * W - 1.f) * 0.5f, fy = ((gy + 1.f) * H - 1.f) * 0.5f;
+      const float x0f = floorf(fx), y0f = floorf(fy);   // (floorf: fx, fy can be negative)
+      const float lx = fx - x0f, ly = fy - y0f;
+      const int x0 = (int)x0f, y0 = (int)y0f;
+      v[0] = v[1] = v[2] = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int y = y0 + (k >> 1), x = x0 + (k & 1);
+        if (y < 0 || x < 0 || y >= H || x >= W) continue;
+        const float wt = ((k >> 1) ? ly : 1.f - ly) * ((k & 1) ? lx : 1.f - lx);
+        float tv[3];
+        aug_tap<RESIZE>(a, img, y, x, dy, dx, flip, ry, rx, tv);
+        v[0] += wt * tv[0];
+        v[1] += wt * tv[1];
+        v[2] += wt * tv[2];
+      }
+    } else {
+      aug_tap<RESIZE>(a, img, i, j, dy, dx, flip, ry, rx, v);
+    }
+    const bool hole = i >= cy0 && i < cy1 && j >= cx0 && j < cx1;
+    bf16x8 o;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      o[c] = f2bf(hole ? 0.f : (v[c] * (1.f / 255.f) - b.mean[c]) * b.inv_std[c]);
+#pragma unroll
+    for (int c = 3; c < 8; ++c) o[c] = f2bf(0.f);
+    *(bf16x8*)(out + (size_t)px * 8) = o;
+  }
+}
+
 constexpr int IS_T = 1024;
 constexpr int MAX_GROUPS = 1024;  // pool batches per pool
 constexpr int IS_LDS_MAX = 128 * 1024;   // dynamic LDS cap (static gsum[] rides on top)
@@ -337,6 +464,18 @@ void pool_build_launch(const PoolBuildArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(pool_take_kernel, dim3(a.P), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(pool_build_kernel, dim3(a.P), dim3(256), 0, st, a);
+}
+
+void pool_augment_launch(const PoolAugmentArgs& a, hipStream_t st) {
+  const dim3 g(a.b.P), blk(256);
+  if (a.affine && a.resize)
+    hipLaunchKernelGGL((pool_augment_kernel<true, true>), g, blk, 0, st, a);
+  else if (a.affine)
+    hipLaunchKernelGGL((pool_augment_kernel<true, false>), g, blk, 0, st, a);
+  else if (a.resize)
+    hipLaunchKernelGGL((pool_augment_kernel<false, true>), g, blk, 0, st, a);
+  else
+    hipLaunchKernelGGL((pool_augment_kernel<false, false>), g, blk, 0, st, a);
 }
 
 size_t is_sample_lds(int P, int alias) {

@@ -145,6 +145,22 @@ struct PoolBuildArgs {
 };
 void pool_build_launch(const PoolBuildArgs& a, hipStream_t st);
 
+// Augmentation recipe (mercury_amd/data/augment.py): Resize -> RandomCrop(pad) -> flip ->
+// RandomAffine(rotation, isotropic scale; bilinear, zeros outside) -> Normalize -> Cutout,
+// evaluated per output pixel in fp32 with no rounding between the stages.
+struct PoolAugmentArgs {
+  PoolBuildArgs b;               // b.shard is [Ns][Hs][Ws][3]; b.H, b.W are the OUTPUT size
+  int Hs, Ws;                    // source image size
+  int resize;                    // 0: off (Hr, Wr = Hs, Ws); else the shorter side's new length
+  int Hr, Wr;                    // size the crop is taken from (transforms.Resize's formula)
+  float degrees;                 // rotation drawn from [-degrees, degrees)
+  float scale_lo, scale_hi;      // isotropic scale drawn from [lo, hi) (lo = hi = 1: unset)
+  int cutout;                    // side of the zeroed square (0: off)
+  int affine;                    // rotation / scale stage on
+  float* params;                 // optional [P][8]: dy, dx, flip, angle_deg, scale, cut_y, cut_x, 0
+};
+void pool_augment_launch(const PoolAugmentArgs& a, hipStream_t st);
+
 struct IsSampleArgs {
   const float* losses;           // [P]
   float* ema;                    // [0] value, [1] initialised flag (device-resident EMAverage)

@@ -36,6 +36,10 @@ class Config:
     dirichlet_alpha: float = 0.5
     batch_size: int = 32
     image_size: int = 32
+    augment: str = 'cifar'          # native engine's pool augmentation: 'cifar' (RandomCrop pad 4 +
+    #                                 flip + CIFAR Normalize) | 'dataset' (read from the loaders'
+    #                                 dataset.transform) | an AugmentRecipe.parse spec, e.g.
+    #                                 'resize=35,crop=32,flip=1,degrees=10,scale=0.9:1.1,norm=none'
     # model / optimisation
     model: str = 'resnet18'
     optimizer: str = 'adam'

@@ -5,6 +5,7 @@ from .datasets import (CIFAR10_truncated, CIFAR100_truncated, My_CIFAR10, Sample
 from .transforms import (CIFAR_MEAN, CIFAR_STD, Compose, Cutout, Normalize, RandomCrop,
                          RandomHorizontalFlip, ToNumpy, ToPILImage, ToTensor,
                          _data_transforms_cifar10)
+from .augment import AugmentRecipe
 from .partition import (partition_data, dirichlet_partition, record_net_data_stats,
                         read_data_distribution, read_net_dataidx_map, get_dataloader,
                         get_dataloader_test, get_dataloader_CIFAR10,

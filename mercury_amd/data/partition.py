@@ -15,8 +15,8 @@ import numpy as np
 import torch.utils.data as data
 
 from .datasets import (CIFAR10_truncated, CIFAR100_truncated, My_CIFAR10, load_cifar_arrays)
-from .transforms import (Compose, RandomAffine, RandomCrop, RandomHorizontalFlip, Resize,
-                         ToTensor, _data_transforms_cifar10)
+from .transforms import (_data_transforms_cifar10, affine_test_transform,
+                         affine_train_transform)
 
 log = logging.getLogger(__name__)
 
@@ -218,9 +218,7 @@ def load_cifar10_noniid(split_num, alpha, batch_size=32, data_dir='./data/cifar1
 def load_cifar10(split_num=1, batch_size=32, root='datasets/cifar10'):
     """IID variant (`exp_dataset.py:21-77`) -> ``(train_loader, presam_loader, test_loader)``."""
     import torch
-    train_set = My_CIFAR10(root, train=True, transform=Compose([
-        Resize(35), RandomCrop(32), RandomHorizontalFlip(),
-        RandomAffine(degrees=10, scale=(0.9, 1.1)), ToTensor()]))
+    train_set = My_CIFAR10(root, train=True, transform=affine_train_transform())
     if split_num > 1:
         subsets = np.array_split(np.arange(len(train_set)), split_num)
         train_loader = data.DataLoader(train_set, batch_size=batch_size, shuffle=True)
@@ -229,7 +227,6 @@ def load_cifar10(split_num=1, batch_size=32, root='datasets/cifar10'):
     else:
         train_loader = data.DataLoader(train_set, batch_size=batch_size, shuffle=True)
         presam_loader = data.DataLoader(train_set, batch_size=batch_size, shuffle=False)
-    test_set = My_CIFAR10(root, train=False, transform=Compose([
-        Resize(33), RandomCrop(32), ToTensor()]))
+    test_set = My_CIFAR10(root, train=False, transform=affine_test_transform())
     test_loader = data.DataLoader(test_set, batch_size=batch_size, shuffle=True)
     return train_loader, presam_loader, test_loader

@@ -6,9 +6,15 @@ HWC uint8 ``numpy`` arrays (what ``CIFAR10_truncated.data`` holds) or CHW float
 tensors after ``ToTensor``.  The randomness uses numpy's global RNG (like
 torchvision uses torch's) so seeded runs are reproducible.
 
-On the GPU hot path none of these run: ``mercury_amd.ops.augment_pool`` does
-crop+flip+normalize for a whole presample pool in one HIP kernel from the
-HBM-resident uint8 shard.
+On the GPU hot path none of these objects run.  ``mercury_amd.ops.pool_build``
+builds a whole presample pool in one HIP kernel from the HBM-resident uint8 shard:
+by default RandomCrop(pad 4) + flip + CIFAR Normalize, or, given an
+``AugmentRecipe`` (``data/augment.py``), the pipeline that recipe describes --
+Resize, RandomCrop, RandomHorizontalFlip, RandomAffine, Normalize, Cutout.
+``AugmentRecipe.from_transform`` reads a ``Compose`` of the classes below into a
+recipe (``Config.augment = 'dataset'``), so the native engine applies what the
+dataset's transform says; the kernel keeps values in float between the stages,
+where ``Resize`` and ``RandomAffine`` here round to uint8 (at most one level apart).
 """
 from __future__ import annotations
 
@@ -105,6 +111,9 @@ class ToTensor(object):
 
 class Normalize(object):
     def __init__(self, mean, std):
+        # (the constructor's own numbers: AugmentRecipe.from_transform reads these)
+        self.mean_values = tuple(float(m) for m in mean)
+        self.std_values = tuple(float(s) for s in std)
         self.mean = torch.tensor(mean, dtype=torch.float32).view(-1, 1, 1)
         self.std = torch.tensor(std, dtype=torch.float32).view(-1, 1, 1)
 
@@ -178,6 +187,17 @@ def cifar_train_transform():
 
 def cifar_test_transform():
     return Compose([ToPILImage(), ToTensor(), Normalize(CIFAR_MEAN, CIFAR_STD)])
+
+
+def affine_train_transform():
+    """The IID loaders' train pipeline (`exp_dataset.py:23-29`); no Normalize."""
+    return Compose([Resize(35), RandomCrop(32), RandomHorizontalFlip(),
+                    RandomAffine(degrees=10, scale=(0.9, 1.1)), ToTensor()])
+
+
+def affine_test_transform():
+    """... and their test pipeline (`exp_dataset.py:63-67`)."""
+    return Compose([Resize(33), RandomCrop(32), ToTensor()])
 
 
 def _data_transforms_cifar10():

@@ -22,6 +22,7 @@ a step costs a handful of host calls.  All buffers are allocated up front.
 """
 from __future__ import annotations
 
+import dataclasses
 import gc
 import math
 import time
@@ -133,7 +134,7 @@ class NativeEngine(object):
                  sampler='alias', exchange_scores=False, global_table=True, score='loss',
                  global_ema=False, autotune=None, force_buckets=False, comm='auto',
                  wire_bf16=False, debug=False, check_order=False, grad_compress=None,
-                 opts=None):
+                 opts=None, augment=None, eval_augment=None):
         ops.lib()
         _warn_hw_queues()
         from ..config import EngineOptions
@@ -148,6 +149,12 @@ class NativeEngine(object):
         self.pool_batches = pool_batches
         self.classes = self.lw.num_classes
         self.H, self.W = image_hw
+        # augmentation recipes (data/augment.py) of the pool builds and of evaluate_arrays;
+        # None: RandomCrop(pad 4) + flip + CIFAR Normalize on a shard of the input size, and
+        # plain Normalize for evaluation
+        self.augment = self._recipe(augment)
+        self.eval_augment = self._recipe(eval_augment)
+        self.aug_params = None           # [P][8] fp32: the last pool's draws (set_shard)
         self.seed = seed
         self.alpha, self.ema_alpha, self.importance = alpha, ema_alpha, importance
         self.world_size = world_size
@@ -787,11 +794,29 @@ class NativeEngine(object):
 
 
     # ------------------------------------------------------------------ data
-    def _device_inputs(self, images):
-        """uint8 HWC images stay uint8 [N][H][W][3] (augmented on the fly); float inputs
-        [N][C][H][W] (e.g. spectrograms) are converted ONCE to NHWC bf16 [N][H][W][8]."""
+    def _recipe(self, recipe):
+        """A recipe whose crop is the network's input size (filled in where it has none)."""
+        if recipe is None:
+            return None
+        recipe = recipe.with_crop((self.H, self.W))
+        if recipe.out_hw != (self.H, self.W):
+            raise ValueError('augmentation recipe crops to %s but the engine was built for '
+                             'image_hw=%s' % (recipe.out_hw, (self.H, self.W)))
+        return recipe
+
+    def _device_inputs(self, images, recipe=None):
+        """uint8 HWC images stay uint8 [N][H][W][3] (augmented on the fly) -- with a recipe,
+        [N][Hs][Ws][3] of any size its crop fits; float inputs [N][C][H][W] (e.g. spectrograms)
+        are converted ONCE to NHWC bf16 [N][H][W][8]."""
         x = torch.as_tensor(np.ascontiguousarray(images)) if not torch.is_tensor(images) \
             else images
+        if x.dtype == torch.uint8 and recipe is not None:
+            if x.dim() != 4 or x.shape[3] != 3:
+                raise ValueError('uint8 shard must be [N][Hs][Ws][3], got %s' % (tuple(x.shape),))
+            recipe.check(x.shape[1], x.shape[2])
+            return x.to(self.device).contiguous()
+        if recipe is not None:
+            raise ValueError('an augmentation recipe needs uint8 HWC images, got %s' % x.dtype)
         if x.dtype == torch.uint8:
             if x.dim() != 4 or tuple(x.shape[1:]) != (self.H, self.W, 3):
                 raise ValueError('uint8 shard must be [N][%d][%d][3], got %s'
@@ -811,9 +836,11 @@ class NativeEngine(object):
     def set_shard(self, images, labels):
         """Keep this rank's training shard resident in HBM: uint8 [Ns][H][W][3] images, or
         float [Ns][C][H][W] inputs pre-converted to NHWC bf16."""
-        x = self._device_inputs(images)
+        x = self._device_inputs(images, self.augment)
         if x.shape[0] < 1:
             raise ValueError('empty shard')
+        if self.augment is not None and self.aug_params is None:
+            self.aug_params = torch.zeros(self.P, 8, dtype=torch.float32, device=self.device)
         # (a shard smaller than one batch -- possible for a Dirichlet non-IID split at large
         # world size -- is cycled: every batch is the shard's epoch permutation, wrapped)
         self.shard = x
@@ -866,7 +893,8 @@ class NativeEngine(object):
             # uniform-sampling baseline: the next batch is the next 32 shard samples
             # (epoch-shuffled, augmented), no pool forward, unit weights
             ops.pool_build(self.shard, self.shard_labels, self.ctrl, sm.input, sm.label,
-                           sm.index, self.B, self.B, self.seed)
+                           sm.index, self.B, self.B, self.seed, recipe=self.augment,
+                           params=self.aug_params)
             self.ctrl[0:1].add_(1)
             self.idx.copy_(self._arange_b)
             self.isw.fill_(1.0)
@@ -879,7 +907,8 @@ class NativeEngine(object):
         # the cursor.  Group sizes stay P, so the table weights need no short-group handling.
         ops.pool_build(self.shard, self.shard_labels, self.ctrl, sm.input, sm.label, sm.index,
                        self.P, self.B, self.seed, zero=sm.stats_arena,
-                       shuffle=self.sampler != 'groupwise')
+                       shuffle=self.sampler != 'groupwise', recipe=self.augment,
+                       params=self.aug_params)
         # (the scoring convs keep their full occupancy: reserving extra LDS per scoring block
         # so train blocks fit beside them measured 1.70-2.21 ms/step vs 1.65 -- in the
         # concurrent step the GPU is throughput-bound, bench/ab_env.sh)
@@ -1424,24 +1453,40 @@ class NativeEngine(object):
         self.opt.pack_weights()
 
     @torch.no_grad()
-    def evaluate_arrays(self, images, labels, batch=500):
+    def evaluate_arrays(self, images, labels, batch=500, augment=None):
         """Eval-mode (running-stats BN) loss / accuracy over uint8 HWC images (or float NCHW
-        inputs) on device."""
-        imgs = self._device_inputs(images)
+        inputs) on device.  ``augment`` (default: the engine's ``eval_augment``): the recipe
+        applied to the images, its random crop included -- drawn from the engine's seed and the
+        batch number, so a second call sees the same views; the batch order is kept."""
+        recipe = self._recipe(augment) if augment is not None else self.eval_augment
+        imgs = self._device_inputs(images, recipe)
         labs = torch.as_tensor(np.asarray(labels), dtype=torch.int64).to(self.device)
         n = imgs.shape[0]
         self.eval_meters.zero_()
         ctrl = torch.zeros(8, dtype=torch.int64, device=self.device)
+        # with a recipe the loss is the ordered fp64 sum of the per-sample losses: the meters'
+        # atomic fp32 sum depends on block arrival order, and fixed random views should give one
+        # number (a forward with split-K convs still moves single losses by an ulp)
+        loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
         done = 0
         while done < n:
             b = min(batch, n - done)
             m = self.mode('eval%d' % b, b, 0, False)
-            ops.pool_build(imgs[done:done + b], labs[done:done + b], ctrl, m.input, m.label,
-                           m.index, b, b, self.seed, augment=False, shuffle=False)
+            if recipe is not None:
+                ops.pool_build(imgs[done:done + b], labs[done:done + b], ctrl, m.input, m.label,
+                               m.index, b, b, self.seed, shuffle=False, recipe=recipe)
+                ctrl[0:1].add_(1)       # (the next batch draws its own crops)
+            else:
+                ops.pool_build(imgs[done:done + b], labs[done:done + b], ctrl, m.input, m.label,
+                               m.index, b, b, self.seed, augment=False, shuffle=False)
             x = self.forward(m)
             self.head(m, x, 'eval', meters=self.eval_meters)
+            if recipe is not None:
+                loss_sum += m.losses[:b].double().sum()
             done += b
         r = self.eval_meters[:3].tolist()
+        if recipe is not None:
+            r[0] = loss_sum.item()
         return r[0] / max(r[1], 1), r[2] / max(r[1], 1), int(r[1])
 
     def global_share(self):
@@ -1469,6 +1514,22 @@ def _dataset_arrays(loader):
     if x is None or y is None:
         raise ValueError('native engine needs a dataset with uint8 HWC .data and .target')
     return np.asarray(x), np.asarray(y)
+
+
+def _config_recipes(cfg, presam_loader, test_loader):
+    """``Config.augment`` -> (train recipe, eval recipe): 'cifar' keeps the engine's built-in
+    pipeline (None, None); 'dataset' reads the loaders' ``dataset.transform``; anything else
+    is an ``AugmentRecipe.parse`` spec, evaluated with its Resize, crop and Normalize only."""
+    from ..data.augment import AugmentRecipe
+    spec = getattr(cfg, 'augment', 'cifar')
+    if spec == 'cifar':
+        return None, None
+    if spec == 'dataset':
+        tr = [getattr(getattr(ld, 'dataset', None), 'transform', None)
+              for ld in (presam_loader, test_loader)]
+        return AugmentRecipe.from_transform(tr[0]), AugmentRecipe.from_transform(tr[1])
+    aug = AugmentRecipe.parse(spec)
+    return aug, dataclasses.replace(aug, flip=False, degrees=0.0, scale=None, cutout=0)
 
 
 class NativeTrainer(Trainer):
@@ -1504,8 +1565,11 @@ class NativeTrainer(Trainer):
         optimizer._opt_called = True
         osp = ops.optimizer_spec(optimizer)       # raises on anything the kernel cannot run
         x, y = _dataset_arrays(presam_loader)
+        aug, eval_aug = _config_recipes(cfg, presam_loader, test_loader)
+        image_hw = tuple(x.shape[1:3]) if aug is None else aug.with_crop(x.shape[1:3]).out_hw
         self.engine = NativeEngine(
-            net, self.device, self.batch_size, cfg.presample_batches, image_hw=x.shape[1:3],
+            net, self.device, self.batch_size, cfg.presample_batches, image_hw=image_hw,
+            augment=aug, eval_augment=eval_aug,
             optimizer=osp['algo'], lr=osp['lr'], betas=osp['betas'], eps=osp['eps'],
             weight_decay=osp['weight_decay'], momentum=osp['momentum'],
             seed=cfg.seed * 1000 + self.rank, alpha=cfg.alpha,

@@ -8,13 +8,50 @@ from ..data.transforms import CIFAR_MEAN, CIFAR_STD
 
 
 def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, pad=4,
-               flip=True, augment=True, mean=CIFAR_MEAN, std=CIFAR_STD, shuffle=True, zero=None):
+               flip=True, augment=True, mean=CIFAR_MEAN, std=CIFAR_STD, shuffle=True, zero=None,
+               recipe=None, params=None, force_augment_kernel=False):
     """Build a P-sample presample pool on device from either the uint8 image shard
     [Ns][H][W][3] (crop/flip/normalise on the fly) or a pre-converted bf16 shard
     [Ns][H][W][8] (non-image inputs: plain gather, no augmentation).  ``zero``: an fp32
-    buffer the same launch zeroes (the scoring pass's BN-statistics arena)."""
+    buffer the same launch zeroes (the scoring pass's BN-statistics arena).
+
+    ``recipe`` (``data.augment.AugmentRecipe``) replaces pad / flip / mean / std by its own
+    pipeline on a uint8 shard [Ns][Hs][Ws][3] of any size the recipe's crop fits; the pool is
+    [P][h][w][8] for its crop (h, w).  A crop-and-flip recipe on a shard of the output size
+    runs the kernel above; ``force_augment_kernel`` sends it through the recipe kernel too
+    (same bits).  ``params``: an fp32 [P][8] buffer that receives each slot's draws
+    (dy, dx, flip, angle_deg, scale, cut_y, cut_x, 0)."""
     _chk(labels, torch.int64, 'labels')
     prebuilt = shard.dtype == torch.bfloat16
+    if recipe is not None:
+        if prebuilt:
+            raise ValueError('an augmentation recipe needs the uint8 image shard, not a '
+                             'pre-converted bf16 one')
+        _chk(shard, torch.uint8, 'shard')
+        if shard.dim() != 4 or shard.shape[-1] != 3:
+            raise ValueError('uint8 shard must be [Ns][Hs][Ws][3]')
+        Ns, Hs, Ws, _ = shard.shape
+        recipe = recipe.with_crop((Hs, Ws))
+        recipe.check(Hs, Ws)
+        pad, flip = recipe.pad, recipe.flip
+        mean, std = recipe.norm()
+        if params is not None or force_augment_kernel or not recipe.is_legacy(Hs, Ws):
+            H, W = recipe.out_hw
+            Hr, Wr = recipe.resized_hw(Hs, Ws)
+            lo, hi = recipe.scale or (1.0, 1.0)
+            _chk(pool, torch.bfloat16, 'pool', P * H * W * 8)
+            if params is not None:
+                _chk(params, torch.float32, 'params', P * 8)
+            lib().pool_augment(ptr(shard), ptr(labels), ptr(ctrl), ptr(pool), ptr(pool_label),
+                               ptr(pool_index), Ns, Hs, Ws, H, W, P, batch, pad, int(flip),
+                               int(augment), int(shuffle), int(seed) & 0xffffffff, list(mean),
+                               [1.0 / s for s in std], stream_ptr(), ptr(zero),
+                               zero.numel() if zero is not None else 0, recipe.resize, Hr, Wr,
+                               recipe.degrees, lo, hi, recipe.cutout, int(recipe.affine),
+                               ptr(params))
+            return
+    elif params is not None or force_augment_kernel:
+        raise ValueError('params / force_augment_kernel need a recipe')
     if not prebuilt:
         _chk(shard, torch.uint8, 'shard')
     elif shard.shape[-1] != 8:
