@@ -15,13 +15,23 @@ struct ConvGeom {
   int Kc;            // reduction length in 8-element chunks = R*S*SC/8
   int Ncols;         // GEMM N (output channels)
   int M;             // GEMM M = images * RP * RQ
-  const bf16* zero;  // 16-byte zero page for padding taps (set by the launcher; kernel arg -> SGPR)
+  const bf16* zero;  // 16-byte zero page (set by the launcher; unused by the igemm loop, which
+                     // gets its zeros from out-of-range buffer offsets)
   // stride-2 dgrad parity class (dgrad_s2_launch): the class is a stride-1 FORWARD gather of dy
   // whose virtual tap (r', s') reads the real weight tap (trb - 2 r', tsb - 2 s') of a [C][R][S][K]
   // weight with row stride ldb; trb < 0: plain (B chunk = k chunk, row stride Kc * 8)
   int ldb = 0;
   int trb = -1, tsb = 0, tS = 0;
+  // byte ranges of the gathered tensor and of the weight: the loop addresses both through
+  // buffer resources with 32-bit byte offsets (set by the launcher, igemm_ranges)
+  unsigned a_bytes = 0, b_bytes = 0;
 };
+
+// Fills g.a_bytes (images * SH * SW * SC * 2) and g.b_bytes (Ncols * row stride * 2); throws
+// std::invalid_argument when either does not fit a 32-bit buffer resource (IGEMM_RANGE_LIM).
+// Every igemm / pair launcher calls it before it launches anything.
+constexpr long long IGEMM_RANGE_LIM = 0xFFFFFF00LL;
+void igemm_ranges(ConvGeom& g, long long images, const char* who);
 
 // BN-backward sums are kept as SUMS_R replicas [SUMS_R][3][C]: a producer block adds into
 // replica (its tile / block index % SUMS_R) and bn_bwd_apply, their one consumer, sums the

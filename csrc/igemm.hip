@@ -28,10 +28,13 @@
 // variant was A/B'd slower on every conv shape of the step and removed in round 3; the 1x1
 // convs that gain from an LDS-DMA pipeline run on the persistent pointwise GEMM, pgemm.hip.)
 // LDS rows are XOR-swizzled (chunk c of row r lives at c ^ (r&7)).  All address math
-// is 32-bit (per-row base offsets + one uniform per-tap offset), padding chunks read
-// a zero page.  Split-K writes fp32 partial tiles in fragment order (16 B per lane,
-// fully coalesced); the last-arriving slice of each tile reduces them and runs the
-// same epilogue inside the launch (see finish()).
+// is 32-bit (per-row base byte offsets + one uniform per-tap offset into a buffer resource per
+// operand), padding chunks take an offset past the resource and load zeros.  Split-K writes
+// fp32 partial tiles in fragment order (16 B per lane, fully coalesced); the last-arriving
+// slice of each tile reduces them and runs the same epilogue inside the launch (see finish()).
+
+#include <stdexcept>
+#include <string>
 
 #include "conv_epi.h"
 #include "wgrad_body.h"
@@ -107,14 +110,40 @@ MA_DEV int tap_offset(const ConvGeom& g, int r, int s) {
   return -(r * g.SW + s) * g.SC;
 }
 
+// Which filter taps of one axis read inside the source, as a bit mask over t = 0..T-1 (T <= 7),
+// for a row whose tap-0 coordinate is x (row_init's h or w) and a source extent of E pixels.
+// The valid taps of an axis are one contiguous range (every second one of it for the stride-2
+// gather), so the mask is two shifts, computed once per row; the loop then tests a bit per tap
+// instead of redoing the coordinate add and range compare for every row of every stage.
+//   forward      : 0 <= x + t < E
+//   dgrad        : 0 <= x - t < E
+//   dgrad, str 2 : x - t even and 0 <= (x - t) / 2 < E
 template <bool TRANS>
-MA_DEV bool tap_ok(const ConvGeom& g, int h, int w, int r, int s) {
-  if (!TRANS) return (unsigned)(h + r) < (unsigned)g.SH && (unsigned)(w + s) < (unsigned)g.SW;
-  const int hp = h - r, wp = w - s;
-  if (g.stride == 2)   // kernel-uniform: scalar branch
-    return ((hp | wp) & 1) == 0 && (unsigned)(hp >> 1) < (unsigned)g.SH &&
-           (unsigned)(wp >> 1) < (unsigned)g.SW;
-  return (unsigned)hp < (unsigned)g.SH && (unsigned)wp < (unsigned)g.SW;
+MA_DEV unsigned axis_mask(int x, int E, int T, int stride) {
+  int lo, hi;              // valid taps: lo <= t < hi
+  unsigned par = ~0u;
+  if (!TRANS) {
+    lo = -x;
+    hi = E - x;
+  } else if (stride == 2) {   // kernel-uniform
+    lo = x - 2 * E + 1;
+    hi = x + 1;
+    par = (x & 1) ? 0xAAu : 0x55u;
+  } else {
+    lo = x - E + 1;
+    hi = x + 1;
+  }
+  lo = min(max(lo, 0), 8);
+  hi = min(max(hi, 0), T);
+  return ((1u << hi) - 1u) & ~((1u << lo) - 1u) & par;   // empty when hi <= lo
+}
+
+// byte offset past every tensor the launchers accept (igemm_ranges): such a load returns zeros
+constexpr unsigned IG_OOB = 0xFFFFFF00u;
+constexpr int IG_RSRC_FLAGS = 0x00020000;   // raw buffer, as wgrad_body's
+
+MA_DEV u32x4 ig_load16(__amdgpu_buffer_rsrc_t rs, unsigned byte_off) {
+  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 0));
 }
 
 // k-chunk -> (r, s, c8) cursor.  When C/8 is a multiple of 8 a 64-deep stage lies in one
@@ -223,39 +252,56 @@ MA_DEV void igemm_nt_body(const bf16* __restrict__ src, const bf16* __restrict__
   const int Kelems = g.Kc * 8;
   const int cc = tid & 7;
 
-  // A rows: the source offset of tap (0, 0) is computed once per row (abase), so a stage's
-  // gather is  abase + uniform tap offset  plus two bounds tests -- no per-row multiplies
-  // (stamps: the per-row multiply-heavy row_at was ~45 % of each stage's cycles).  A row
-  // past M gets an out-of-range h, so its bounds test always fails.
-  int abase[AR], ah[AR], aw[AR];
+  // Both operands through buffer resources with 32-bit byte offsets (as wgrad_body): a padding
+  // tap, a row past M / Ncols, a chunk past K or past this split's range gets the offset IG_OOB,
+  // beyond the resource, and loads zeros -- no zero-page pointer select and no 64-bit address
+  // arithmetic per load.  The ranges are the tensors' exact byte counts (igemm_ranges).
+  const auto rsa = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, g.a_bytes, IG_RSRC_FLAGS);
+  const auto rsb = __builtin_amdgcn_make_buffer_rsrc((void*)wt, 0, g.b_bytes, IG_RSRC_FLAGS);
+
+  // A rows: the byte offset of tap (0, 0) is computed once per row (abase), so a stage's
+  // gather is  abase + uniform tap offset  -- no per-row multiplies (stamps: the per-row
+  // multiply-heavy row_at was ~45 % of each stage's cycles) -- and the row's valid filter rows
+  // and columns are bit masks (amask: rows in bits 0..6, columns in bits 8..14), so a tap's
+  // bounds test is one AND + compare against the stage's tap bits.  The masks are per lane:
+  // on the KCursor slow path the lanes of one stage sit in different taps.  A row past M has
+  // an empty mask.
+  unsigned abase[AR], amask[AR];
 #pragma unroll
   for (int i = 0; i < AR; ++i) {
-    int off;
-    row_init<TRANS>(g, m0 + (tid >> 3) + 32 * i, off, ah[i], aw[i]);
-    abase[i] = row_base<TRANS>(g, off, ah[i], aw[i]);
-    if (off < 0) ah[i] = -(1 << 28);
+    int off, h, w;
+    row_init<TRANS>(g, m0 + (tid >> 3) + 32 * i, off, h, w);
+    abase[i] = (unsigned)row_base<TRANS>(g, off, h, w) * 2u;
+    const unsigned hm = axis_mask<TRANS>(h, g.SH, g.R, g.stride);
+    const unsigned wm = axis_mask<TRANS>(w, g.SW, g.S, g.stride);
+    amask[i] = off >= 0 ? hm | (wm << 8) : 0u;
   }
-  int boff[BR];
+  unsigned boff[BR];
+  bool bval[BR];
   const int ldb = g.ldb ? g.ldb : Kelems;
 #pragma unroll
   for (int i = 0; i < BR; ++i) {
     const int n = n0 + (tid >> 3) + 32 * i;
-    boff[i] = n < g.Ncols ? n * ldb : -1;
+    bval[i] = n < g.Ncols;
+    boff[i] = (unsigned)n * (unsigned)ldb * 2u;
   }
   KCursor kc;
   kc.init(g, kt0);
-  const bf16* zp = g.zero;
 
   // prologue state for the chunk in flight (PRO only; dead code otherwise)
   float4 pst[8];
   int pz = 0;
-  int pko[AR];
+  unsigned pko[AR];    // byte offset of the kept chunk in pro.keep, or IG_OOB
   u32x4 prs[AR];       // residual chunks (pro.res)
   const float* pbase = nullptr;
   if constexpr (PRO) {
     const int grp = m0 / pro.group_rows;
     pbase = pro.stats ? pro.stats + (size_t)grp * 2 * g.SC : nullptr;
   }
+  // the residual has the A source's shape; a null one is an empty range
+  const auto rsr = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(PRO ? pro.res : nullptr), 0, PRO && pro.res != nullptr ? g.a_bytes : 0u,
+      IG_RSRC_FLAGS);
   auto load_stage = [&](int kt, u32x4 (&ra)[AR], u32x4 (&rb)[BR]) {
     int r, s, c8;
     bool kval;
@@ -278,25 +324,31 @@ MA_DEV void igemm_nt_body(const bf16* __restrict__ src, const bf16* __restrict__
       keep = pro.keep != nullptr && nt == 0 && kval && r * g.S + s == pro.keep_tap;
       pz = 0;
     }
-    const int toff = tap_offset<TRANS>(g, r, s) + c8 * 8;
+    const unsigned toff = (unsigned)(tap_offset<TRANS>(g, r, s) + c8 * 8) * 2u;
+    // the stage's tap as bits of amask; a chunk that loads nothing asks for bit 31, which no
+    // row has (r, s <= 6 on every lane, also where kval is false)
+    const unsigned tbits = kval ? (1u << r) | (0x100u << s) : 0x80000000u;
     // B chunk: the k chunk itself, or (parity class) the real weight tap of virtual tap (r, s)
     const int bch = g.trb < 0 ? kt * 8 + cc
                               : ((g.trb - 2 * r) * g.tS + (g.tsb - 2 * s)) * (g.SC >> 3) + c8;
+    const unsigned bcol = (unsigned)bch * 16u;
+    // every thread issues AR + BR (+ AR residual) loads every call, whatever is valid: a select
+    // on the offset, not a branch around the load, so hipcc's counted vmcnt stays exact
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
-      const bool ok = kval && tap_ok<TRANS>(g, ah[i], aw[i], r, s);
-      const int o = abase[i] + toff;
-      ra[i] = *(const u32x4*)(ok ? src + o : zp);   // select, not a branch around the gather
+      const bool ok = (amask[i] & tbits) == tbits;
+      const unsigned o = ok ? abase[i] + toff : IG_OOB;
+      ra[i] = ig_load16(rsa, o);
       if constexpr (PRO) {
         pz |= (ok ? 0 : 1) << i;
-        pko[i] = keep && ok ? o : -1;
-        if (pro.res != nullptr) prs[i] = *(const u32x4*)(ok ? pro.res + o : zp);
+        pko[i] = keep ? o : IG_OOB;
+        if (pro.res != nullptr) prs[i] = ig_load16(rsr, o);
       }
     }
 #pragma unroll
     for (int i = 0; i < BR; ++i) {
-      const bool ok = kval && boff[i] >= 0;
-      rb[i] = *(const u32x4*)(ok ? wt + boff[i] + bch * 8 : zp);
+      const bool ok = kval && bval[i];
+      rb[i] = ig_load16(rsb, ok ? boff[i] + bcol : IG_OOB);
     }
   };
   auto store_stage = [&](int buf, u32x4 (&ra)[AR], const u32x4 (&rb)[BR]) {
@@ -333,7 +385,7 @@ MA_DEV void igemm_nt_body(const bf16* __restrict__ src, const bf16* __restrict__
         }
         const u32x4 t = __builtin_bit_cast(u32x4, o);
         ra[i] = ((pz >> i) & 1) ? u32x4{0u, 0u, 0u, 0u} : t;
-        if (pko[i] >= 0) *(u32x4*)(pro.keep + pko[i]) = ra[i];
+        if (pko[i] != IG_OOB) *(u32x4*)((char*)pro.keep + pko[i]) = ra[i];
       }
     }
 #pragma unroll
@@ -744,10 +796,31 @@ const bf16* conv_zero_page() {
   return zp;
 }
 
+// The loop's buffer resources cover exactly the gathered tensor ([images][SH][SW][SC] bf16) and
+// the weight ([Ncols][row stride] bf16).  Refuse, before anything is launched, a geometry whose
+// ranges do not fit 32-bit byte offsets below IG_OOB.
+void igemm_ranges(ConvGeom& g, long long images, const char* who) {
+  const long long a = images * g.SH * g.SW * g.SC * 2;
+  const long long ldb = g.ldb ? (long long)g.ldb : (long long)g.Kc * 8;
+  const long long b = (long long)g.Ncols * ldb * 2;
+  if (images < 0 || a < 0 || b < 0 || a >= IGEMM_RANGE_LIM || b >= IGEMM_RANGE_LIM)
+    throw std::invalid_argument(std::string(who) +
+                                ": tensors must be < 4 GB (32-bit buffer offsets)");
+  g.a_bytes = (unsigned)a;
+  g.b_bytes = (unsigned)b;
+}
+
+// images of a plain geometry: M = images * RP * RQ
+static long long geom_images(const ConvGeom& g) {
+  const long long pq = (long long)g.RP * g.RQ;
+  return pq > 0 ? g.M / pq : 0;
+}
+
 void igemm_launch(const bf16* src, const bf16* wt, const ConvGeom& g_in, const EpiParams& e,
                   int bm, int bn, int splits, bool trans, hipStream_t st, const ProParams* pro) {
   ConvGeom g = g_in;
   g.zero = zero_page();
+  igemm_ranges(g, geom_images(g), "igemm");
 #define MA_CASE(BM_, BN_)                                                           \
   if (bm == BM_ && bn == BN_) {                                                     \
     if (trans) launch_cfg<BM_, BN_, true>(src, wt, g, e, splits, st, nullptr);       \
@@ -769,6 +842,8 @@ int igemm_dual_launch(const bf16* srcA, const bf16* wtA, const ConvGeom& gA, con
                       const EpiParams& eB, int splitsB, int bm, int bn, hipStream_t st) {
   IgProb A{srcA, wtA, gA, eA, 0, 0, 0}, B{srcB, wtB, gB, eB, 0, 0, 0};
   A.g.zero = B.g.zero = zero_page();
+  igemm_ranges(A.g, geom_images(A.g), "igemm_dual");
+  igemm_ranges(B.g, geom_images(B.g), "igemm_dual");
   ig_grid(A.g, bm, bn, splitsA, A.gx, A.per, A.gy);
   ig_grid(B.g, bm, bn, splitsB, B.gx, B.per, B.gy);
   if (A.gy == 1) A.e.slab = nullptr;
@@ -833,6 +908,7 @@ static bool s2_geom(const ConvGeom& gt, int bm, int bn, int H, int W, int N, S2G
     g.trb = trb < 0 ? 0 : trb;
     g.tsb = tsb < 0 ? 0 : tsb;
     g.tS = gt.S;
+    igemm_ranges(g, N, "dgrad_s2");       // dy: N images whatever the class's row space
     sg.g[c] = g;
     sg.hc[c] = hc;
     sg.wc[c] = wc;
@@ -903,6 +979,7 @@ int conv_bwd_pair_sc_launch(const bf16* dyA, const bf16* wtA, const ConvGeom& gA
   A.wt = wtA;
   A.g = gA_in;
   A.g.zero = zero_page();
+  igemm_ranges(A.g, geom_images(A.g), "conv_bwd_pair_sc");
   A.e = eA_in;
   A.x = xA;
   A.wg = wgA_in;
@@ -943,6 +1020,7 @@ int conv_bwd_pair_launch(const bf16* dy, const bf16* wt, const ConvGeom& g_in, c
                          float* dw, int wbm, int wbn, int wsplits, hipStream_t st) {
   ConvGeom g = g_in;
   g.zero = zero_page();
+  igemm_ranges(g, geom_images(g), "conv_bwd_pair");
   WgradGeom wg = wg_in;
   wg.zero = g.zero;
 #define MA_W(DBM_, DBN_, WBM_, WBN_)                                                   \

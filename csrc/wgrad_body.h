@@ -74,20 +74,32 @@ MA_DEV void wgrad_body(const bf16* __restrict__ dy, const bf16* __restrict__ x, 
   // A (dy) rows: pixel pixA + i * (NT / ACH), channel chunk k; advanced by BKP pixels a stage
   const int k = m0 + acc_ * 8;
   int pixA = pt0 * BKP + tid / ACH;
-  // B (x) rows: the source pixel's (n, p, q), advanced by BKP pixels a stage without a division
-  // (q += BKP % Q, p += BKP / Q, carries); a 1x1 stride-1 conv reads x at the dy pixel itself
+  // B (x) rows: the source pixel's coordinates (h, w) and its byte offset are carried from stage
+  // to stage -- a stage moves the dy pixel BKP forward, i.e. by (an, ap, aq) in (n, p, q) with at
+  // most one carry out of q and one out of p, each a compare and conditional adds -- so a row
+  // costs no division, no multiply and no loop per stage; a 1x1 stride-1 conv reads x at the dy
+  // pixel itself.  The image index is not carried: n < N is the dy pixel being below npix.
   const bool pw = g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0;
-  const int aq = BKP % g.Q, ap = BKP / g.Q;
+  const int pqB = g.P * g.Q;
+  const int an = BKP / pqB, arem = BKP - an * pqB;
+  const int ap = arem / g.Q, aq = arem - ap * g.Q;
+  const int xrow = g.W * g.C * 2, xpix = g.C * 2;                  // bytes per x row / pixel
+  const int dstage = an * g.H * xrow + ap * g.stride * xrow + aq * g.stride * xpix;
+  const int dq = g.stride * xrow - g.Q * g.stride * xpix;          // q -= Q, ++p
+  const int dp = g.H * xrow - g.P * g.stride * xrow;               // p -= P, ++n
+  const int wlim = g.Q * g.stride - g.pad + xs, hlim = g.P * g.stride - g.pad + xr;
   int pixB = pt0 * BKP + tid / BCH;
-  int bn_[BR], bp_[BR], bq_[BR];
+  int bh_[BR], bw_[BR];
+  unsigned bo_[BR];
 #pragma unroll
   for (int i = 0; i < BR; ++i) {
     const int pix = pixB + i * (NT / BCH);
-    const int pq = g.P * g.Q;
-    bn_[i] = pix / pq;
-    const int rem = pix - bn_[i] * pq;
-    bp_[i] = rem / g.Q;
-    bq_[i] = rem - bp_[i] * g.Q;
+    const int n = pix / pqB;
+    const int rem = pix - n * pqB;
+    const int p = rem / g.Q, q = rem - p * g.Q;
+    bh_[i] = p * g.stride - g.pad + xr;
+    bw_[i] = q * g.stride - g.pad + xs;
+    bo_[i] = (unsigned)(((n * g.H + bh_[i]) * g.W + bw_[i]) * g.C + xc8 * 8) * 2u;
   }
   // stage loads into a register set; a stage past this split's range loads zeros, so every
   // trip issues the same number of loads and hipcc's counted vmcnt stays exact
@@ -110,22 +122,24 @@ MA_DEV void wgrad_body(const bf16* __restrict__ dy, const bf16* __restrict__ x, 
         ok = live && jval && pix < npix;
         off = (unsigned)(pix * g.C + xc8 * 8) * 2u;
       } else {
-        const int h = bp_[i] * g.stride - g.pad + xr, ww = bq_[i] * g.stride - g.pad + xs;
-        ok = live && jval && bn_[i] < g.N && (unsigned)h < (unsigned)g.H &&
+        const int pix = pixB + i * (NT / BCH);
+        int h = bh_[i], ww = bw_[i];
+        ok = live && jval && pix < npix && (unsigned)h < (unsigned)g.H &&
              (unsigned)ww < (unsigned)g.W;
-        off = (unsigned)(((bn_[i] * g.H + h) * g.W + ww) * g.C + xc8 * 8) * 2u;
-        int q = bq_[i] + aq, p = bp_[i] + ap, n = bn_[i];
-        if (q >= g.Q) {
-          q -= g.Q;
-          ++p;
-        }
-        while (p >= g.P) {
-          p -= g.P;
-          ++n;
-        }
-        bn_[i] = n;
-        bp_[i] = p;
-        bq_[i] = q;
+        off = bo_[i];
+        unsigned o = off + (unsigned)dstage;
+        h += ap * g.stride;
+        ww += aq * g.stride;
+        const bool cq = ww >= wlim;
+        ww -= cq ? g.Q * g.stride : 0;
+        h += cq ? g.stride : 0;
+        o += cq ? (unsigned)dq : 0u;
+        const bool cp = h >= hlim;
+        h -= cp ? g.P * g.stride : 0;
+        o += cp ? (unsigned)dp : 0u;
+        bh_[i] = h;
+        bw_[i] = ww;
+        bo_[i] = o;
       }
       rb[i] = __builtin_bit_cast(u32x4,
                                  __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? off : BAD, 0, 0));
