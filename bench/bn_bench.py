@@ -39,7 +39,6 @@ def main():
     args = ap.parse_args()
     import torch
     from mercury_amd import ops
-    lib = ops.lib()
     dev = 'cuda'
     for name, M, C, G, rm in SHAPES:
         if args.shapes and name not in args.shapes.split(','):
@@ -61,12 +60,12 @@ def main():
         nbytes = M * C * 2 * (2 + (1 if rm else 0))
         ref = None
         for v in [int(x) for x in args.variants.split(',')]:
-            lib.bn_configure(0 if v else 1 << 62)
             fn = lambda: ops.bn_apply(y, stats, gamma, beta, out, M, C, group_rows=gr,  # noqa
                                       act='relu', res=res, res_bn=res_bn)
-            us = gtime(fn, reps=args.reps)
-            fn()
-            torch.cuda.synchronize()
+            with ops.streaming_stores(0 if v else 1 << 62):
+                us = gtime(fn, reps=args.reps)
+                fn()
+                torch.cuda.synchronize()
             same = None
             if ref is None:
                 ref = out.clone()
@@ -75,7 +74,6 @@ def main():
             print(json.dumps({'shape': name, 'M': M, 'C': C, 'res': rm, 'variant': v,
                               'us': round(us, 2), 'tbps': round(nbytes / us / 1e6, 2),
                               'equal': same}), flush=True)
-        lib.bn_configure(256 << 20)
         del y, res, out, ref
         torch.cuda.empty_cache()
 

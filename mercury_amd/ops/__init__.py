@@ -5,7 +5,8 @@ raw launcher in ``mercury_amd._C`` on the *current* HIP stream (so every call
 is capturable into a HIP graph).  There is no silent fallback: on a machine
 with a GPU, a missing or stale extension raises.  The plain-PyTorch fp32
 oracles the kernels are tested against live in ``tests/refutil.py`` and in each
-GPU test; the CPU path is the eager ``mercury_amd.trainer.Trainer``.
+GPU test, the fp64 ones of the BN / pooling / head kernels in ``tests/kernel_oracles.py``;
+the CPU path is the eager ``mercury_amd.trainer.Trainer``.
 
 Layout conventions: activations NHWC bf16 with channels padded to a multiple
 of 8; conv weights bf16 [K][R][S][Cpad] (forward) and [C][R][S][K] (dgrad);
@@ -107,7 +108,7 @@ def _chk(t, dtype, name, numel=None):
 
 from .conv import (ConvSpec, conv_fwd, conv_fwd_dual, conv_dgrad, conv_wgrad, conv_bwd, pick_tiles, pack_conv_weight,  # noqa: E402
                    to_nhwc, from_nhwc, pgemm_fwd, pwconv_fwd, stem_fwd)
-from .bn import bn_apply, bn_bwd, BnRunTable, sums_numel, sums_total  # noqa: E402
+from .bn import bn_apply, bn_bwd, BnRunTable, sums_numel, sums_total, streaming_stores  # noqa: E402
 from .head import head_fwd, head_bwd, mlp_head_fwd, mlp_head_bwd  # noqa: E402
 from .importance import pool_build, is_sample, gather  # noqa: E402
 from .table import ImportanceTable  # noqa: E402
@@ -117,7 +118,7 @@ from .misc import (quantize, pool2d_fwd, maxpool2d_bwd, dwconv_fwd, dwconv_dgrad
                    nchw_to_nhwc8, tern_pack, tern_unpack)
 
 __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_fwd', 'pwconv_fwd', 'stem_fwd', 'conv_dgrad', 'conv_wgrad', 'conv_bwd', 'pick_tiles',
-           'pack_conv_weight', 'to_nhwc', 'from_nhwc', 'bn_apply', 'bn_bwd', 'BnRunTable', 'sums_numel', 'sums_total',
+           'pack_conv_weight', 'to_nhwc', 'from_nhwc', 'bn_apply', 'bn_bwd', 'BnRunTable', 'sums_numel', 'sums_total', 'streaming_stores',
            'head_fwd', 'head_bwd', 'mlp_head_fwd', 'mlp_head_bwd', 'pool_build', 'is_sample', 'gather', 'ImportanceTable',
            'FlatOptimizer', 'optimizer_spec', 'quantize', 'tern_pack', 'tern_unpack', 'pool2d_fwd', 'maxpool2d_bwd',
            'dwconv_fwd', 'dwconv_dgrad', 'dwconv_wgrad', 'dwconv_wgrad_slab_floats',

@@ -1,11 +1,30 @@
 """BatchNorm / activation / residual front-end (kernels in ``csrc/bn.hip``)."""
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from . import _chk, lib, ptr, stream_ptr
 
 ACT = {'none': 0, 'relu': 1, 'relu6': 2}
+
+# bn_apply outputs of at least this many bytes leave through streaming (nontemporal) stores
+# (csrc/bn.hip g_bn_nt_min)
+NT_MIN_BYTES = 256 << 20
+# bn_bwd's kernels fold their sums through static LDS arrays of [3][2048] floats
+MAX_BWD_C = 2048
+
+
+@contextlib.contextmanager
+def streaming_stores(min_bytes):
+    """Within the block, bn_apply outputs of at least ``min_bytes`` bytes use streaming stores
+    (0: every launch, 1 << 62: none); the default threshold is restored on exit."""
+    lib().bn_configure(int(min_bytes))
+    try:
+        yield
+    finally:
+        lib().bn_configure(NT_MIN_BYTES)
 
 
 def bn_apply(y, stats, gamma, beta, out, M, C, group_rows=0, act='relu', eps=1e-5,
@@ -54,6 +73,9 @@ def bn_bwd(dout, out, y, stats, gamma, sums, dy, M, C, act='relu', eps=1e-5, y2=
     the caller zeroes a whole arena once per step (one memset instead of one per layer).
     ``reduce=False``: the sums were already reduced by the producing dgrad's epilogue
     (``conv_dgrad(bw=...)``) -- only the apply pass runs."""
+    if C > MAX_BWD_C:
+        # refused here, before the workspace is zeroed: a refused call launches and writes nothing
+        raise ValueError('bn_bwd: at most %d channels' % MAX_BWD_C)
     _chk(sums, torch.float32, 'sums', sums_numel(C))
     if zero_sums and reduce:
         sums.zero_()

@@ -23,6 +23,8 @@ def head_fwd(act, w, b, label, B, HW, C, classes, mode, pooled=None, logits=None
     act(bn(act) [+ res]) -- dict(gamma, beta, eps, act, res=None, and stats + count +
     group_imgs (ghost / batch statistics) or rmean + rvar (running)) -- instead of reading a
     block output that a bn_apply pass wrote."""
+    if score == 'gradnorm' and logits is not None and pooled is None:
+        raise ValueError('head_fwd: the gradnorm score over ready logits reads pooled[]')
     _chk(act, torch.bfloat16, 'act', B * HW * C)
     _chk(w, torch.float32, 'w', classes * C)
     _chk(label, torch.int32, 'label', B)
