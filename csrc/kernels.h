@@ -347,3 +347,27 @@ void dwconv_wgrad_launch(const bf16* dy, const bf16* x, float* dw, int N, int H,
                          size_t slab_floats = 0);
 void nchw_to_nhwc8_launch(const float* x, bf16* y, int N, int C, int H, int W, int Cpad,
                           hipStream_t st);
+// bidirectional LSTM recurrence, one launch per time step, both directions per launch (lstm.hip).
+// Step s handles t = s for direction 0 and t = T-1-s for direction 1 (the backward walks the
+// other way: t = T-1-s and t = s).
+struct LstmFwdArgs {
+  const float* pre;               // [T][2][B][4H] x . W_ih^T + b_ih + b_hh, gates i, f, g, o
+  const bf16* whh;                // [2][4H][H]
+  bf16* out;                      // [T][B][2H]; h_t at column dir*H, read back as the next h_prev
+  float* c;                       // train: [T][2][B][H] every c_t; else [2][B][H], updated in place
+  bf16* gates;                    // train: [T][2][B][4H] post-activation gates; else null
+  const bf16* h0;                 // [2][B][H] initial state, or null = zero
+  const float* c0;                // [2][B][H], or null = zero
+  int T, B, H, s, train;
+};
+void lstm_step_fwd_launch(const LstmFwdArgs& a, hipStream_t st);
+struct LstmBwdArgs {                // of a forward that started from a zero state
+  const float* dout;              // [T][B][2H] upstream gradient of out
+  const bf16* gates;              // saved by the forward
+  const float* c;                 // [T][2][B][H] saved by the forward
+  const bf16* whhT;               // [2][H][4H] = W_hh transposed
+  bf16* dG;                       // [T][2][B][4H] pre-activation gradients; step s reads step s-1's
+  float* dc;                      // [2][B][H] dc_next in, dc_prev out (in place); step 0 reads zero
+  int T, B, H, s;
+};
+void lstm_step_bwd_launch(const LstmBwdArgs& a, hipStream_t st);

@@ -116,6 +116,8 @@ from .optim import FlatOptimizer, optimizer_spec  # noqa: E402
 from .misc import (quantize, pool2d_fwd, maxpool2d_bwd, dwconv_fwd, dwconv_dgrad, dwconv_wgrad, dwconv_wgrad_slab_floats,
                    dwconv_bwd, dwconv_wgrad_reduce_batch, dwconv_wgrad_blocks,  # noqa: E402
                    nchw_to_nhwc8, tern_pack, tern_unpack)
+from .lstm import (lstm_step_fwd, lstm_step_bwd, pack_lstm, BiLSTMFunction, bilstm, emulate,  # noqa: E402
+                   MEASURED_NATIVE)
 
 __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_fwd', 'pwconv_fwd', 'stem_fwd', 'conv_dgrad', 'conv_wgrad', 'conv_bwd', 'pick_tiles',
            'pack_conv_weight', 'to_nhwc', 'from_nhwc', 'bn_apply', 'bn_bwd', 'BnRunTable', 'sums_numel', 'sums_total', 'streaming_stores',
@@ -123,4 +125,5 @@ __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_f
            'FlatOptimizer', 'optimizer_spec', 'quantize', 'tern_pack', 'tern_unpack', 'pool2d_fwd', 'maxpool2d_bwd',
            'dwconv_fwd', 'dwconv_dgrad', 'dwconv_wgrad', 'dwconv_wgrad_slab_floats',
            'dwconv_bwd', 'dwconv_wgrad_reduce_batch', 'dwconv_wgrad_blocks',
-           'nchw_to_nhwc8']
+           'nchw_to_nhwc8', 'lstm_step_fwd', 'lstm_step_bwd', 'pack_lstm', 'BiLSTMFunction', 'bilstm',
+           'emulate', 'MEASURED_NATIVE']
