@@ -24,7 +24,13 @@
 // so later consumers see the layout they want).
 //
 // Main loop: 256 threads = 4 waves (2x2), BK = 64 per stage, register-staged double buffer
-// (stage t+1 loads issued before stage t's MFMAs, one barrier per stage).  (An LDS-DMA ring
+// (stage t+1 loads issued before stage t's MFMAs, one barrier per stage).  The latency-bound
+// launches (64-wide tiles on a grid that does not fill the chip twice over, every pair dgrad)
+// keep TWO stages in flight in registers (PF = 2): the loop is unrolled by two, runs whole trips
+// only and leaves through its bound alone, and the last one or two stages are straight-line
+// code behind it -- so the only vmcnt waits in the loop are the counted ones in front of each
+// stage's LDS writes and the other register set's loads stay outstanding across the trip
+// boundary (bench/isa_wait_seq.py prints the structure from a listing).  (An LDS-DMA ring
 // variant was A/B'd slower on every conv shape of the step and removed in round 3; the 1x1
 // convs that gain from an LDS-DMA pipeline run on the persistent pointwise GEMM, pgemm.hip.)
 // LDS rows are XOR-swizzled (chunk c of row r lives at c ^ (r&7)).  All address math
@@ -409,24 +415,35 @@ MA_DEV void igemm_nt_body(const bf16* __restrict__ src, const bf16* __restrict__
   if (kt0 < kt1 && PF == 2) {
     // two stages in flight in registers (the train-batch dgrad is latency-bound: a 64-deep
     // stage is a few MFMAs per wave against a memory round trip); unrolled by two so each
-    // register set is named statically, every trip issues the same loads (counted vmcnt exact)
+    // register set is named statically, every trip issues the same loads (counted vmcnt exact).
+    // The loop runs whole trips only and has no exit but its bound: the last one or two stages
+    // are straight-line code behind it.  (With a `break` after each MFMA phase hipcc routed
+    // both exits through the latch block, so the header had a predecessor in which the set just
+    // loaded was the newest thing outstanding, and the wait-count pass drained every load at the
+    // top of a trip -- the second stage in flight was lost.)
     u32x4 ra0[AR], rb0[BR], ra1[AR], rb1[BR];
+    const bf16* a1 = sA + Smem<BM, BN>::STAGE;
     load_stage(kt0, ra0, rb0);
     store_stage(0, ra0, rb0);
-    load_stage(kt0 + 1, ra1, rb1);
+    load_stage(kt0 + 1, ra1, rb1);       // past kt1 for a one-stage range: zeros, never stored
     __syncthreads();
-    for (int kt = kt0; kt < kt1; kt += 2) {
+    int kt = kt0;
+    for (; kt + 2 < kt1; kt += 2) {
       load_stage(kt + 2, ra0, rb0);      // LDS 0 holds stage kt, ra1 stage kt + 1
       mma_stage<BM, BN>(sA, sA + BM * BK, acc, lane, wm, wn);
-      if (kt + 1 >= kt1) break;
       store_stage(1, ra1, rb1);
       __syncthreads();
       load_stage(kt + 3, ra1, rb1);      // LDS 1 holds stage kt + 1, ra0 stage kt + 2
-      const bf16* a1 = sA + Smem<BM, BN>::STAGE;
       mma_stage<BM, BN>(a1, a1 + BM * BK, acc, lane, wm, wn);
-      if (kt + 2 >= kt1) break;
       store_stage(0, ra0, rb0);
       __syncthreads();
+    }
+    // tail: LDS 0 holds stage kt, ra1 stage kt + 1 if the range has one; no further loads
+    mma_stage<BM, BN>(sA, sA + BM * BK, acc, lane, wm, wn);
+    if (kt + 1 < kt1) {
+      store_stage(1, ra1, rb1);
+      __syncthreads();
+      mma_stage<BM, BN>(a1, a1 + BM * BK, acc, lane, wm, wn);
     }
     __syncthreads();                     // the epilogue may reuse the stage LDS
   } else if (kt0 < kt1) {
@@ -574,6 +591,18 @@ void dual_cfg(IgProb A, IgProb B, hipStream_t st) {
       return;
     }
   }
+  // 128 x 128 (the scoring pass's stride-2 block heads: 9-36 stages per block on a grid of
+  // 1280): two stages in flight at any grid size.  With the PF = 2 loop keeping both sets
+  // outstanding the second set pays here too -- 191 VGPRs, no spill, still two blocks per CU
+  // (64 KB of stages each); same box, interleaved, scoring solo 0.9705 / 0.9705 / 0.9722 ->
+  // 0.9529 / 0.9505 / 0.9590 ms and the step 1.2266 / 1.2277 / 1.2290 -> 1.2121 / 1.2127 /
+  // 1.2115 ms (profiles/r9/pf_waits/bench_ab.json).
+#ifndef MERCURY_DUAL128_PF1   // (A/B builds: bench/build_variant.py with this flag)
+  if constexpr (BM == 128 && BN == 128) {
+    hipLaunchKernelGGL((igemm_dual_kernel<BM, BN, 2>), dim3(grid), dim3(NT), 0, st, A, B);
+    return;
+  }
+#endif
   hipLaunchKernelGGL((igemm_dual_kernel<BM, BN, 1>), dim3(grid), dim3(NT), 0, st, A, B);
 }
 

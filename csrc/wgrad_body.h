@@ -24,9 +24,15 @@ struct WgSmem {
 };
 
 // One (column tile bx, pixel split by) of the weight-gradient GEMM; gy = number of splits.
-// PF: stages in flight in registers -- 2 where the extra register set fits (64-wide tiles),
-// 1 for 128 x 128 (the second set spilled)
-template <int BM, int BN, int PF = (BM * BN <= 64 * 128 ? 2 : 1)>
+// PF: stages in flight in registers -- 2 for the 64-wide tiles, 1 for 128 x 128.  (With the
+// exit-free PF = 2 loop the second set no longer spills at 128 x 128 -- 238 VGPRs in the pair
+// kernels, still two blocks per CU -- but it buys nothing: the ResNet-18 step 1.2152 / 1.2171 /
+// 1.2179 ms with PF 1 vs 1.2180 / 1.2166 / 1.2161 with PF 2, same box, interleaved; ResNet-50
+// and VGG11 equal too.  profiles/r9/pf_waits/bench_ab.json.)
+#ifndef MERCURY_WG_PF2_AREA   // (A/B builds: bench/build_variant.py with -DMERCURY_WG_PF2_AREA=16384)
+#define MERCURY_WG_PF2_AREA (64 * 128)
+#endif
+template <int BM, int BN, int PF = (BM * BN <= MERCURY_WG_PF2_AREA ? 2 : 1)>
 MA_DEV void wgrad_body(const bf16* __restrict__ dy, const bf16* __restrict__ x, const WgradGeom& g,
                        float* __restrict__ dw, int ptiles_per_split, bf16* smem, int bx, int by,
                        int gy) {
@@ -215,23 +221,32 @@ MA_DEV void wgrad_body(const bf16* __restrict__ dy, const bf16* __restrict__ x, 
   } else if (pt0 < pt1) {
     // two stages in flight in registers (the train-batch wgrad is latency-bound: a 64-pixel
     // stage is ~8 MFMAs per wave, far shorter than a memory round trip), LDS double-buffered;
-    // unrolled by two so each register set is named statically
+    // unrolled by two so each register set is named statically.  Whole trips only, no exit but
+    // the loop bound, and the last one or two stages as straight-line code behind the loop: a
+    // `break` after each MFMA phase made hipcc drain every load at the top of a trip (see
+    // igemm_nt_body's PF = 2 loop).
     u32x4 ra0[AR], rb0[BR], ra1[AR], rb1[BR];
     load_stage(pt0, ra0, rb0);
     store_stage(0, ra0, rb0);
-    load_stage(pt0 + 1, ra1, rb1);
+    load_stage(pt0 + 1, ra1, rb1);       // past pt1 for a one-stage range: zeros, never stored
     __syncthreads();
-    for (int pt = pt0; pt < pt1; pt += 2) {
+    int pt = pt0;
+    for (; pt + 2 < pt1; pt += 2) {
       load_stage(pt + 2, ra0, rb0);      // LDS 0 holds stage pt, ra1 stage pt + 1
       mma(0);
-      if (pt + 1 >= pt1) break;
       store_stage(1, ra1, rb1);
       __syncthreads();
       load_stage(pt + 3, ra1, rb1);      // LDS 1 holds stage pt + 1, ra0 stage pt + 2
       mma(1);
-      if (pt + 2 >= pt1) break;
       store_stage(0, ra0, rb0);
       __syncthreads();
+    }
+    // tail: LDS 0 holds stage pt, ra1 stage pt + 1 if the range has one; no further loads
+    mma(0);
+    if (pt + 1 < pt1) {
+      store_stage(1, ra1, rb1);
+      __syncthreads();
+      mma(1);
     }
   }
 
