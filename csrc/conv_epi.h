@@ -112,9 +112,239 @@ MA_DEV int phys_row(const EpiParams& e, int row) {
   return (n * e.rm_h + 2 * i + e.rm_ph) * e.rm_w + 2 * j + e.rm_pw;
 }
 
-template <int BM, int BN, int WM = 2>
+// ---------------------------------------------------------------- prefetched row operands
+// What the row loop of a dgrad epilogue reads besides the accumulators -- the old dst of an
+// accumulating dgrad, the BN-backward operands (bw_out, bw_y, bw_y2) and the BN statistics --
+// was final before the launch started and a thread's (row, chunk) pairs are fixed at block
+// entry, so igemm_nt_body requests all of it in front of its last MFMA phases and the epilogue
+// finds it in registers instead of paying up to five dependent memory round trips behind the
+// last MFMA.  Every operand goes through a buffer resource based at the tile's first output
+// row: a row >= M or a chunk column >= N takes the offset EPI_OOB (loads zeros, stores
+// nothing), an absent operand a resource of zero bytes -- no branch round any load or store,
+// so the counted vmcnt waits stay exact.
+constexpr unsigned EPI_OOB = 0x80000000u;
+constexpr int EPI_RSRC_FLAGS = 0x00020000;    // raw buffer
+constexpr int EPI_RANGE = 0x7fffffff;
+
+// K-split launches: every block of a tile requests the operands in front of its tail, though
+// only the last arriver uses them.  Measured against requesting them in the block that wins the
+// tile's ticket, under its slab reads (-DMERCURY_EPI_PF_WINNER, bench/build_variant.py; same
+// box, interleaved, ResNet-18 step): 1.1868 / 1.1848 ms against 1.1939 / 1.1924 / 1.1920, parent
+// 1.2158 / 1.2141 / 1.2137 (profiles/r10/dgrad_epi/bench_ab.json) -- the losers' requests mostly
+// hit L2 lines the winner then finds there, the winner's own come a ticket round trip later.
+#ifdef MERCURY_EPI_PF_WINNER
+constexpr bool EPI_PF_ALL = false;
+#else
+constexpr bool EPI_PF_ALL = true;
+#endif
+
+MA_DEV u32x4 epi_load16(__amdgpu_buffer_rsrc_t rs, unsigned byte_off) {
+  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 0));
+}
+
+// EARLY (the 64 x 64 two-stage kernels, igemm_nt_body): both trips of the row loop are requested
+// in front of the last MFMA phases, and the tile's statistics as ONE dword per thread (wave w
+// loads row w of [sum, sumsq, shortcut sum, shortcut sumsq] x 64 columns), handed round through
+// LDS in the epilogue -- as 16-byte chunks per thread they were 32 more registers across the
+// tail, a block per CU.  Otherwise the loads go out at the top of the row loop: two trips at a
+// time, or one where a second set would cost the 64 x 64 one-stage kernels a block per CU.
+template <int BM, int BN, bool EARLY>
+struct EpiPf {
+  static constexpr bool EARLY_ = EARLY;
+  static constexpr int CPR = BN / 8, TRIPS = BM * CPR / NT;
+  static constexpr int G = EARLY || TRIPS > 2 ? 2 : 1;   // trips held in registers at a time
+  static_assert(NT % CPR == 0 && TRIPS * NT == BM * CPR && TRIPS % G == 0, "row loop shape");
+  static_assert(!EARLY || (BN * 4 == NT && TRIPS == 2), "EARLY: 64 x 64 tiles");
+  unsigned off[TRIPS];   // byte offset of the thread's chunk in trip t from the tile's first
+                         // output row, or EPI_OOB
+  u32x4 old[G], ao[G], ay[G], ay2[G];
+  unsigned sv;           // EARLY: the thread's statistics dword
+
+  MA_DEV void init(const EpiParams& e, int M, int N, int m0, int n0) {
+    const int tid = threadIdx.x, colc = n0 + (tid % CPR) * 8;
+    const int pr0 = phys_row(e, m0);
+#pragma unroll
+    for (int t = 0; t < TRIPS; ++t) {
+      const int row = m0 + tid / CPR + t * (NT / CPR);
+      const bool ok = row < M && colc < N;
+      const int d = phys_row(e, ok ? row : m0) - pr0;
+      off[t] = ok ? (unsigned)(d * e.ldo + colc) * 2u : EPI_OOB;
+    }
+  }
+};
+
+// The tile's resources: out / bw_out / bw_y / bw_y2 from the tile's first output row (32-bit
+// offsets inside a tile whatever the tensor's size), a statistics row with its exact range.
+// Each is built where it is used (four scalar registers each; all at once spilled some).
+MA_DEV __amdgpu_buffer_rsrc_t epi_rsrc(const void* p, bool on, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(on ? p : nullptr), 0, on ? bytes : 0,
+                                           EPI_RSRC_FLAGS);
+}
+MA_DEV size_t epi_base(const EpiParams& e, int m0) { return (size_t)phys_row(e, m0) * e.ldo; }
+
+// request trips [g * G, g * G + G) of the row loop; every thread issues the same 4 * G loads
+template <class P>
+MA_DEV void epi_load_rows(P& pf, const EpiParams& e, int m0, int g) {
+  constexpr int G = P::G;
+  const size_t base = epi_base(e, m0);
+  const bool bw = e.bw_sums != nullptr, two = bw && e.bw_y2 != nullptr;
+  const auto ro = epi_rsrc(e.out + base, e.accumulate != 0, EPI_RANGE);
+#pragma unroll
+  for (int u = 0; u < G; ++u) pf.old[u] = epi_load16(ro, pf.off[g * G + u]);
+  const auto ra = epi_rsrc(e.bw_out + base, bw, EPI_RANGE);
+#pragma unroll
+  for (int u = 0; u < G; ++u) pf.ao[u] = epi_load16(ra, pf.off[g * G + u]);
+  const auto ry = epi_rsrc(e.bw_y + base, bw, EPI_RANGE);
+#pragma unroll
+  for (int u = 0; u < G; ++u) pf.ay[u] = epi_load16(ry, pf.off[g * G + u]);
+  const auto ry2 = epi_rsrc(e.bw_y2 + base, two, EPI_RANGE);
+#pragma unroll
+  for (int u = 0; u < G; ++u) pf.ay2[u] = epi_load16(ry2, pf.off[g * G + u]);
+}
+
+// the prefetch: (EARLY) the thread's statistics dword, then the first G trips
+template <class P>
+MA_DEV void epi_prefetch(P& pf, const EpiParams& e, int m0, int n0, int N) {
+  if constexpr (P::EARLY_) {
+    const bool bw = e.bw_sums != nullptr, two = bw && e.bw_y2 != nullptr;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // statistics row
+    const float* row = (w < 2 ? e.bw_stats : e.bw_stats2) + (w & 1) * e.ldo;
+    const auto rs = epi_rsrc(row, bw && (w < 2 || two), e.ldo * 4);
+    const int col = n0 + (threadIdx.x & 63);
+    pf.sv = __builtin_amdgcn_raw_buffer_load_b32(rs, col < N ? (unsigned)col * 4u : EPI_OOB, 0, 0);
+  }
+  epi_load_rows(pf, e, m0, 0);
+}
+
+// Sums over the lanes that differ in bit 4 and in bit 5 without the LDS pipe.  The swaps
+// exchange whole rows / halves between TWO registers, so each step also packs two partial sums
+// into one register: v_permlane16_swap a, b leaves a = [a.r0 b.r0 a.r2 b.r2] and
+// b = [a.r1 b.r1 a.r3 b.r3] (rows of 16 lanes), their sum holds a's pair sums in rows 0 / 2 and
+// b's in rows 1 / 3; v_permlane32_swap does the same with the halves.  Four registers come out
+// as one whose row r holds the total of register r -- the same pairs in the same order as the
+// xor-16 / xor-32 butterfly.
+MA_DEV float swap16_sum(float a, float b) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a),
+                                                  __builtin_bit_cast(unsigned, b), false, false);
+  const unsigned r0 = r[0], r1 = r[1];
+  return __builtin_bit_cast(float, r0) + __builtin_bit_cast(float, r1);
+}
+MA_DEV float swap32_sum(float a, float b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a),
+                                                  __builtin_bit_cast(unsigned, b), false, false);
+  const unsigned r0 = r[0], r1 = r[1];
+  return __builtin_bit_cast(float, r0) + __builtin_bit_cast(float, r1);
+}
+// v + (lane ^ 8's v): DPP row_ror:8
+MA_DEV float ror8_sum(float v) {
+  return v + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x128,
+                                                                0xF, 0xF, false));
+}
+
+// Row loop of the dgrad epilogues, fully unrolled, on prefetched operands.  MODE 0: stores
+// only; 1: + BN-backward sums; 2: + the shortcut BN's sum.  MODE and ACC are block-uniform and
+// resolved outside (epilogue), so the element code has no branch: the activation mask is two
+// compares and a select.
+template <int BM, int BN, bool EARLY, int MODE, bool ACC>
+MA_DEV void epi_rows(EpiPf<BM, BN, EARLY>& pf, const bf16* tile, float* red, const EpiParams& e,
+                     int m0, int n0, int N) {
+  using P = EpiPf<BM, BN, EARLY>;
+  constexpr int CPR = P::CPR, TRIPS = P::TRIPS, G = P::G, LDT = BN + 8;
+  const int tid = threadIdx.x, lane = tid & 63, ch = tid % CPR;
+  const auto rso = epi_rsrc(e.out + epi_base(e, m0), true, EPI_RANGE);
+  float mean[8], rstd[8], mean2[8], rstd2[8], sdz[8], sx[8], sx2[8];
+  float alo, ahi;
+  bn_act_bounds(e.bw_act, alo, ahi);
+  const bool pass = e.bw_act == 0;
+  if constexpr (MODE >= 1) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) sdz[k] = sx[k] = sx2[k] = 0.f;
+    if constexpr (EARLY) {   // the statistics rows the epilogue staged behind the sums
+      const float* sl = red + 8 * BN + ch * 8;
+      bn_mean_rstd8(sl, BN, e.bw_inv_count, e.bw_eps, mean, rstd);
+      if constexpr (MODE == 2)
+        bn_mean_rstd8(sl + 2 * BN, BN, e.bw_inv_count, e.bw_eps, mean2, rstd2);
+    } else {
+      const int colc = n0 + ch * 8, cc = colc < N ? colc : 0;
+      bn_mean_rstd8(e.bw_stats + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean, rstd);
+      if constexpr (MODE == 2)
+        bn_mean_rstd8(e.bw_stats2 + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean2, rstd2);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < TRIPS; ++t) {
+    const int u = t % G;
+    if (u == 0 && t > 0) epi_load_rows(pf, e, m0, t / G);
+    const int rl = tid / CPR + t * (NT / CPR);
+    bf16x8 v = *(const bf16x8*)(tile + rl * LDT + ch * 8);
+    if constexpr (ACC) {
+      const bf16x8 o = __builtin_bit_cast(bf16x8, pf.old[u]);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = f2bf(bf2f(v[k]) + bf2f(o[k]));
+    }
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rso, pf.off[t], 0, 0);
+    if constexpr (MODE >= 1) {
+      const bool valid = pf.off[t] != EPI_OOB;
+      const bf16x8 ao = __builtin_bit_cast(bf16x8, pf.ao[u]);
+      const bf16x8 ay = __builtin_bit_cast(bf16x8, pf.ay[u]);
+      const bf16x8 ay2 = __builtin_bit_cast(bf16x8, pf.ay2[u]);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float ok = bf2f(ao[k]);
+        const bool keep = valid & (pass | ((ok > alo) & (ok < ahi)));
+        const float dz = keep ? bf2f(v[k]) : 0.f;
+        sdz[k] += dz;
+        sx[k] += dz * (bf2f(ay[k]) - mean[k]) * rstd[k];
+        if constexpr (MODE == 2) sx2[k] += dz * (bf2f(ay2[k]) - mean2[k]) * rstd2[k];
+      }
+    }
+  }
+  if constexpr (MODE >= 1) {
+    // lanes ch, ch + CPR, ... of a wave share the chunk: sum them pairwise in the butterfly's
+    // order (xor 8 by DPP where CPR == 8, then the packed xor 16 / xor 32 steps above), which
+    // leaves the total of register 4 q + r in row r of packed register q; then one LDS atomic
+    // per (wave, column), then one global atomic per column per block
+    constexpr int NV = MODE == 2 ? 24 : 16;
+    float vals[NV];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      vals[k] = sdz[k];
+      vals[8 + k] = sx[k];
+      if constexpr (MODE == 2) vals[16 + k] = sx2[k];
+    }
+    if constexpr (CPR == 8) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) vals[i] = ror8_sum(vals[i]);
+    }
+    static_assert(CPR == 8 || CPR == 16, "chunks per row");
+    const int r = lane >> 4;
+    const bool first = CPR == 16 || (lane & 8) == 0;
+#pragma unroll
+    for (int q = 0; q < NV / 4; ++q) {
+      const float s = swap32_sum(swap16_sum(vals[4 * q], vals[4 * q + 1]),
+                                 swap16_sum(vals[4 * q + 2], vals[4 * q + 3]));
+      const int idx = 4 * q + r;
+      if (first) atomicAdd(&red[(idx >> 3) * BN + ch * 8 + (idx & 7)], s);
+    }
+    __syncthreads();
+    // replica (row tile % SUMS_R) of the [SUMS_R][3][ldo] sums (igemm.h)
+    float* sums = e.bw_sums + (size_t)((m0 / BM) % SUMS_R) * 3 * e.ldo;
+    for (int i = tid; i < BN; i += NT) {
+      const int col = n0 + i;
+      if (col < N) {
+        atomicAdd(sums + col, red[i]);
+        atomicAdd(sums + e.ldo + col, red[BN + i]);
+        if constexpr (MODE == 2) atomicAdd(sums + 2 * e.ldo + col, red[2 * BN + i]);
+      }
+    }
+  }
+}
+
+// BWT: a dgrad instantiation (igemm_nt_body) -- its row loop runs on operands prefetched into
+// ``pf``; every other instantiation carries no BN-backward code at all.
+template <int BM, int BN, int WM = 2, bool BWT = false, bool EARLY = false>
 MA_DEV void epilogue(AccT<BM, BN, WM>& acc, char* smem, const EpiParams& e, int M, int N,
-                     int m0, int n0) {
+                     int m0, int n0, EpiPf<BM, BN, EARLY>* pf = nullptr) {
   constexpr int WN = 4 / WM, TM = BM / (16 * WM), TN = BN / (16 * WN), LDT = BN + 8;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wm = w / WN, wn = w % WN;
@@ -212,6 +442,10 @@ MA_DEV void epilogue(AccT<BM, BN, WM>& acc, char* smem, const EpiParams& e, int 
       }
     }
   }
+  if constexpr (BWT && EARLY) {
+    // the prefetched statistics dwords -> red[8 BN ..): sum, sumsq, shortcut sum, shortcut sumsq
+    if (bw) red[8 * BN + tid] = __builtin_bit_cast(float, pf->sv);
+  }
   MA_STAMP(9);
   __syncthreads();
   if (stats) {
@@ -234,6 +468,30 @@ MA_DEV void epilogue(AccT<BM, BN, WM>& acc, char* smem, const EpiParams& e, int 
   }
   // coalesced 16-byte row stores from the staged tile.  NT is a multiple of CPR, so every
   // thread keeps ONE 8-column chunk for the whole loop (its BN constants load once).
+  MA_STAMP(10);
+  if constexpr (BWT) {
+    // dgrad: unrolled row loop on the prefetched operands; the block-uniform options select one
+    // of six straight-line instances here, outside the element code
+    static_assert(WM == 2, "the prefetched row loop serves igemm_nt_body");
+    if constexpr (!EARLY) {
+      // not requested ahead of the MFMA tail (igemm_nt_body): request here, where the
+      // accumulators are dead -- the first two trips and the statistics in one round trip
+      pf->init(e, M, N, m0, n0);
+      epi_prefetch(*pf, e, m0, n0, N);
+    }
+    const bool two = bw && e.bw_y2 != nullptr;
+    if (!bw) {
+      if (e.accumulate) epi_rows<BM, BN, EARLY, 0, true>(*pf, tile, red, e, m0, n0, N);
+      else epi_rows<BM, BN, EARLY, 0, false>(*pf, tile, red, e, m0, n0, N);
+    } else if (!two) {
+      if (e.accumulate) epi_rows<BM, BN, EARLY, 1, true>(*pf, tile, red, e, m0, n0, N);
+      else epi_rows<BM, BN, EARLY, 1, false>(*pf, tile, red, e, m0, n0, N);
+    } else {
+      if (e.accumulate) epi_rows<BM, BN, EARLY, 2, true>(*pf, tile, red, e, m0, n0, N);
+      else epi_rows<BM, BN, EARLY, 2, false>(*pf, tile, red, e, m0, n0, N);
+    }
+    return;
+  }
   constexpr int CPR = BN / 8;
   const int ch = tid % CPR;
   const int colc = n0 + ch * 8;
@@ -249,7 +507,6 @@ MA_DEV void epilogue(AccT<BM, BN, WM>& acc, char* smem, const EpiParams& e, int 
     bn_mean_rstd8(e.bw_stats + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean, rstd);
     if (two) bn_mean_rstd8(e.bw_stats2 + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean2, rstd2);
   }
-  MA_STAMP(10);
   for (int i = tid; i < BM * CPR; i += NT) {
     const int rl = i / CPR;
     const int row = m0 + rl, col = colc;
@@ -322,9 +579,10 @@ MA_DEV void epilogue(AccT<BM, BN, WM>& acc, char* smem, const EpiParams& e, int 
 // counter is reset by the last arriver (slabs are zero-initialised at allocation).
 constexpr int SEM_INTS = 1024;   // tile counters at the head of the slab (4 KB)
 
-template <int BM, int BN, int WM = 2>
+template <int BM, int BN, int WM = 2, bool BWT = false, bool EARLY = false>
 MA_DEV void finish(AccT<BM, BN, WM>& acc, char* smem, const EpiParams& e, int M, int N,
-                   int m0, int n0, int bx, int by, int gx, int gy) {
+                   int m0, int n0, int bx, int by, int gx, int gy,
+                   EpiPf<BM, BN, EARLY>* pf = nullptr) {
   constexpr int TM = BM / (16 * WM), TN = BN * WM / 64;
   if (e.slab) {
     const int ntiles = gx;
@@ -352,6 +610,9 @@ MA_DEV void finish(AccT<BM, BN, WM>& acc, char* smem, const EpiParams& e, int M,
     __syncthreads();
     if (!flag[0]) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // keep the sc1 loads below the ticket
+    // (EPI_PF_WINNER builds) the epilogue's operands, requested by the one block that will use
+    // them, in flight under the slab reads
+    if constexpr (BWT && EARLY && !EPI_PF_ALL) epi_prefetch(*pf, e, m0, n0, N);
     for (int sp = 0; sp < splits; ++sp) {
       if (sp == by) continue;
       const int base = (sp * ntiles + bx) * tile_bytes + threadIdx.x * 16;
@@ -365,7 +626,7 @@ MA_DEV void finish(AccT<BM, BN, WM>& acc, char* smem, const EpiParams& e, int M,
     }
     __syncthreads();   // flag read by every wave before the epilogue reuses smem
   }
-  epilogue<BM, BN, WM>(acc, smem, e, M, N, m0, n0);
+  epilogue<BM, BN, WM, BWT, EARLY>(acc, smem, e, M, N, m0, n0, pf);
 }
 
 }  // namespace

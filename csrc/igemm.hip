@@ -238,7 +238,11 @@ MA_DEV void mma_stage(const bf16* a, const bf16* b, f32x4 (&acc)[BM / 32][BN / 3
 // (ProParams in igemm.h).  Everything it needs for the chunk staged next -- the 8 channels'
 // statistics / gamma / beta, which rows are padding, where the activation is kept -- is loaded
 // or computed in load_stage, so it is in flight under the MFMA phase like the tile itself.
-template <int BM, int BN, bool TRANS, bool PRO = false, int PF = 1>
+// BWT: a dgrad instantiation -- the epilogue's row operands (old dst of an accumulating dgrad,
+// BN-backward operands and statistics: conv_epi.h EpiPf) are requested ahead of their use: in
+// front of the last MFMA phases (EARLY, below; by every block of a K-split tile, see
+// EPI_PF_ALL), else in batches at the top of the epilogue's row loop.
+template <int BM, int BN, bool TRANS, bool PRO = false, int PF = 1, bool BWT = TRANS>
 MA_DEV void igemm_nt_body(const bf16* __restrict__ src, const bf16* __restrict__ wt,
                           const ConvGeom& g, const EpiParams& e, int ktiles_per_split, char* smem,
                           int bx, int by, int gx, int gy, const ProParams& pro) {
@@ -412,6 +416,16 @@ MA_DEV void igemm_nt_body(const bf16* __restrict__ src, const bf16* __restrict__
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // EARLY: the latency-bound dgrad launches (64 x 64 tiles, PF == 2).  Their whole row loop is
+  // two trips and fits in registers next to the main loop's at the same blocks per CU; every
+  // other dgrad instantiation requests its trips in batches at the top of the row loop (the
+  // wider tiles would lose a block per CU to the registers, and requested inside the PF == 1
+  // loop the operands became loop-carried registers that hipcc spilled).
+  constexpr bool EARLY = BWT && PF == 2 && BM * BN == 64 * 64;
+  EpiPf<BM, BN, EARLY> pf;
+  // block-uniform: this block requests the epilogue operands in front of its last MFMA phase
+  const bool pf_tail = EARLY && (EPI_PF_ALL || e.slab == nullptr);
+
   if (kt0 < kt1 && PF == 2) {
     // two stages in flight in registers (the train-batch dgrad is latency-bound: a 64-deep
     // stage is a few MFMAs per wave against a memory round trip); unrolled by two so each
@@ -426,6 +440,7 @@ MA_DEV void igemm_nt_body(const bf16* __restrict__ src, const bf16* __restrict__
     load_stage(kt0, ra0, rb0);
     store_stage(0, ra0, rb0);
     load_stage(kt0 + 1, ra1, rb1);       // past kt1 for a one-stage range: zeros, never stored
+    if constexpr (EARLY) pf.init(e, g.M, g.Ncols, m0, n0);   // under the first loads
     __syncthreads();
     int kt = kt0;
     for (; kt + 2 < kt1; kt += 2) {
@@ -438,7 +453,11 @@ MA_DEV void igemm_nt_body(const bf16* __restrict__ src, const bf16* __restrict__
       store_stage(0, ra0, rb0);
       __syncthreads();
     }
-    // tail: LDS 0 holds stage kt, ra1 stage kt + 1 if the range has one; no further loads
+    // tail: LDS 0 holds stage kt, ra1 stage kt + 1 if the range has one; no further stage
+    // loads -- the epilogue's operands go out here, under the last one or two MFMA phases
+    if constexpr (EARLY) {
+      if (pf_tail) epi_prefetch(pf, e, m0, n0, g.Ncols);
+    }
     mma_stage<BM, BN>(sA, sA + BM * BK, acc, lane, wm, wn);
     if (kt + 1 < kt1) {
       store_stage(1, ra1, rb1);
@@ -477,9 +496,13 @@ MA_DEV void igemm_nt_body(const bf16* __restrict__ src, const bf16* __restrict__
         for (int q = 0; q < 4; ++q) g_stamps[b_][4 + q] = lap[q];
     }
 #endif
+  } else if constexpr (EARLY) {
+    // an empty reduction (a parity class no tap reaches): zeros, same epilogue
+    pf.init(e, g.M, g.Ncols, m0, n0);
+    if (pf_tail) epi_prefetch(pf, e, m0, n0, g.Ncols);
   }
   MA_STAMP(2);
-  finish<BM, BN>(acc, smem, e, g.M, g.Ncols, m0, n0, bx, by, gx, gy);
+  finish<BM, BN, 2, BWT, EARLY>(acc, smem, e, g.M, g.Ncols, m0, n0, bx, by, gx, gy, &pf);
   MA_STAMP(3);
 }
 
@@ -637,8 +660,8 @@ __global__ __launch_bounds__(NT, (nt_occ<BM, BN>())) void dgrad_s2_kernel(const 
   ec.rm_pw = c & 1;
   const ProParams none{};
   const int bx = b - sg.pre[c];
-  igemm_nt_body<BM, BN, false, false, PF>(dy, wt, sg.g[c], ec, 1 << 20, smem, bx, 0,
-                                          sg.pre[c + 1] - sg.pre[c], 1, none);
+  igemm_nt_body<BM, BN, false, false, PF, true>(dy, wt, sg.g[c], ec, 1 << 20, smem, bx, 0,
+                                                sg.pre[c + 1] - sg.pre[c], 1, none);
 }
 
 template <int BM, int BN>
@@ -709,7 +732,7 @@ __global__ __launch_bounds__(NT, 2) void bwd_pair_s2_kernel(const bf16* __restri
   ec.rm_ph = c >> 1;
   ec.rm_pw = c & 1;
   const ProParams none{};
-  igemm_nt_body<DBM, DBN, false, false, PAIR_PF<DBM, DBN>()>(
+  igemm_nt_body<DBM, DBN, false, false, PAIR_PF<DBM, DBN>(), true>(
       dy, wt, sg.g[c], ec, 1 << 20, smem, d - sg.pre[c], 0, sg.pre[c + 1] - sg.pre[c], 1, none);
 }
 
@@ -776,9 +799,9 @@ __global__ __launch_bounds__(NT, 2) void bwd_pair_sc_kernel(PairProb A, S2PairPr
   ec.rm_w = B.sg.W;
   ec.rm_ph = c >> 1;
   ec.rm_pw = c & 1;
-  igemm_nt_body<64, 64, false, false, PAIR_PF<64, 64>()>(B.dy, B.wt, B.sg.g[c], ec, 1 << 20, smem,
-                                                         d - B.sg.pre[c], 0,
-                                                         B.sg.pre[c + 1] - B.sg.pre[c], 1, none);
+  igemm_nt_body<64, 64, false, false, PAIR_PF<64, 64>(), true>(
+      B.dy, B.wt, B.sg.g[c], ec, 1 << 20, smem, d - B.sg.pre[c], 0, B.sg.pre[c + 1] - B.sg.pre[c],
+      1, none);
 }
 
 template <int DBM, int DBN, int WBM, int WBN>
@@ -892,7 +915,8 @@ int igemm_dual_launch(const bf16* srcA, const bf16* wtA, const ConvGeom& gA, con
 }
 
 // the four class geometries of a stride-2 dgrad (false: the conv does not qualify)
-static bool s2_geom(const ConvGeom& gt, int bm, int bn, int H, int W, int N, S2Geom& sg) {
+static bool s2_geom(const ConvGeom& gt, int bm, int bn, int H, int W, int N, int ldo,
+                    S2Geom& sg) {
   // gt: the TRANS geometry (SH, SW = dy spatial, SC = dy channels, R, S, stride, pad, Ncols = C)
   if (gt.stride != 2 || (gt.SC & 63) || gt.R != gt.S) return false;
   if (!((gt.R == 3 && gt.pad == 1) || (gt.R == 1 && gt.pad == 0))) return false;
@@ -919,6 +943,11 @@ static bool s2_geom(const ConvGeom& gt, int bm, int bn, int H, int W, int N, S2G
     // supported shapes (3x3 pad 1, 1x1 pad 0), so the class gather is stride 1, pad 0
     if ((rv && ph + gt.pad - trb != 0) || (sv && pw + gt.pad - tsb != 0)) return false;
     const int hc = (H - ph + 1) / 2, wc = (W - pw + 1) / 2;
+    // the epilogue addresses a tile's output rows by 32-bit byte offsets from its first row
+    // (conv_epi.h EpiPf): bm class rows lie within bm / (hc * wc) + 2 images
+    if (hc * wc > 0 && ((long long)bm / (hc * wc) + 2) * H * W * ldo * 2 >= (1ll << 31))
+      throw std::invalid_argument(
+          "dgrad_s2: an output tile must span < 2 GB (32-bit buffer offsets)");
     ConvGeom g{};
     g.SH = gt.SH;
     g.SW = gt.SW;
@@ -949,7 +978,7 @@ static bool s2_geom(const ConvGeom& gt, int bm, int bn, int H, int W, int N, S2G
 int dgrad_s2_launch(const bf16* dy, const bf16* wt, const ConvGeom& gt, const EpiParams& e_in,
                     int bm, int bn, int H, int W, int N, hipStream_t st) {
   S2Geom sg;
-  if (!s2_geom(gt, bm, bn, H, W, N, sg)) return 0;
+  if (!s2_geom(gt, bm, bn, H, W, N, e_in.ldo, sg)) return 0;
   EpiParams e = e_in;
   e.slab = nullptr;                     // one K slice per tile
 #define MA_CASE(BM_, BN_)                    \
@@ -971,7 +1000,7 @@ int conv_bwd_pair_s2_launch(const bf16* dy, const bf16* wt, const ConvGeom& gt,
                             const bf16* x, const WgradGeom& wg_in, float* dw, int wbm, int wbn,
                             int wsplits, hipStream_t st) {
   S2Geom sg;
-  if (!s2_geom(gt, bm, bn, H, W, N, sg)) return 0;
+  if (!s2_geom(gt, bm, bn, H, W, N, e_in.ldo, sg)) return 0;
   EpiParams e = e_in;
   e.slab = nullptr;
   WgradGeom wg = wg_in;
@@ -1019,7 +1048,7 @@ int conv_bwd_pair_sc_launch(const bf16* dyA, const bf16* wtA, const ConvGeom& gA
   wgb::wg_grid(A.wg, wbm, wbn, wsplits, A.wgx, A.wper, A.wgy);
   if (A.wgx > wgb::WG_SEM_INTS) A.wg.slab = nullptr;
   S2PairProb B;
-  if (!s2_geom(gtB, 64, 64, HB, WB, NB, B.sg)) return 0;
+  if (!s2_geom(gtB, 64, 64, HB, WB, NB, eB_in.ldo, B.sg)) return 0;
   B.dy = dyB;
   B.wt = wtB;
   B.e = eB_in;
