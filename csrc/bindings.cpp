@@ -548,6 +548,35 @@ PYBIND11_MODULE(_C, m) {
     check_launch("lstm_step_bwd");
   });
 
+  // attention pooling over time (attn.hip)
+  m.def("attn_pool_split", [](int T, int B) {
+    int share = 0, nsb = 0;
+    attn_pool_split(T, B, &share, &nsb);
+    return std::make_pair(share, nsb);
+  });
+  m.def("attn_pool_fwd", [](uintptr_t x, uintptr_t w, uintptr_t lengths, uintptr_t rep,
+                            uintptr_t attn, uintptr_t score, uintptr_t ws, long long ws_floats,
+                            long long xst, long long xsb, int T, int B, int D, int bf16_x,
+                            uintptr_t st) {
+    AttnFwdArgs a{P<const void>(x), P<const float>(w), P<const int>(lengths), P<float>(rep),
+                  P<float>(attn), P<float>(score), P<float>(ws), ws_floats, xst, xsb,
+                  T, B, D, bf16_x};
+    attn_pool_fwd_launch(a, S(st));
+    check_launch("attn_pool_fwd");
+  });
+  m.def("attn_pool_bwd", [](uintptr_t x, uintptr_t w, uintptr_t g, uintptr_t rep, uintptr_t attn,
+                            uintptr_t score, uintptr_t lengths, uintptr_t dx, uintptr_t dw,
+                            uintptr_t ws, long long ws_floats, long long xst, long long xsb,
+                            long long dst, long long dsb, int T, int B, int D, int bf16_x,
+                            uintptr_t st) {
+    AttnBwdArgs a{P<const void>(x), P<const float>(w), P<const float>(g), P<const float>(rep),
+                  P<const float>(attn), P<const float>(score), P<const int>(lengths),
+                  P<void>(dx), P<float>(dw), P<float>(ws), ws_floats, xst, xsb, dst, dsb,
+                  T, B, D, bf16_x};
+    attn_pool_bwd_launch(a, S(st));
+    check_launch("attn_pool_bwd");
+  });
+
   m.def("pool_build", [](uintptr_t shard, uintptr_t labels, uintptr_t ctrl, uintptr_t pool,
                          uintptr_t pool_label, uintptr_t pool_index, int Ns, int H, int W, int Pn,
                          int batch, int pad, int flip, int augment, int shuffle, uint32_t seed,

@@ -371,3 +371,44 @@ struct LstmBwdArgs {                // of a forward that started from a zero sta
   int T, B, H, s;
 };
 void lstm_step_bwd_launch(const LstmBwdArgs& a, hipStream_t st);
+// attention pooling over time (attn.hip): s = x . w, a = masked softmax_t(relu(s)),
+// rep = sum_t a x.  x / dx are addressed by element strides for t and b with the D row
+// contiguous; a block of ATTN_BLOCK_WAVES waves takes one batch row and that many shares of
+// T (attn_pool_split) and leaves one partial; a second launch merges the partials in order.
+constexpr int ATTN_WAVE_FRAMES = 8;     // smallest share of T one wave walks
+constexpr int ATTN_BLOCK_WAVES = 4;
+constexpr int ATTN_MAX_SPLITS = 32;     // most wave shares T is cut into
+constexpr int ATTN_TARGET_WAVES = 2048; // T is cut until B * shares reaches this
+constexpr int ATTN_MAX_D = 2048;
+// share: frames per wave; nsb: blocks (partials) per batch row
+void attn_pool_split(int T, int B, int* share, int* nsb);
+struct AttnFwdArgs {
+  const void* x;                  // fp32 or bf16 (bf16_x), element (t, b) at x + t*st + b*sb
+  const float* w;                 // [D]
+  const int* lengths;             // [B], clamped to [0, T] here; null = T
+  float* rep;                     // [B][D]
+  float* attn;                    // [B][T]
+  float* score;                   // [B][T] s before the relu (training), or null
+  float* ws;                      // >= B * nsb * (D + 2) floats
+  long long ws_floats;
+  long long st, sb;
+  int T, B, D, bf16_x;
+};
+void attn_pool_fwd_launch(const AttnFwdArgs& a, hipStream_t st);
+struct AttnBwdArgs {
+  const void* x;                  // as the forward read it
+  const float* w;                 // [D]
+  const float* g;                 // [B][D] upstream gradient of rep
+  const float* rep;               // [B][D] forward output: c_b = g_b . rep_b
+  const float* attn;              // [B][T] forward output
+  const float* score;             // [B][T] saved s: ds is zero where s <= 0
+  const int* lengths;             // as the forward's
+  void* dx;                       // x's dtype, element (t, b) at dx + t*dst + b*dsb; every frame
+                                  // is written, frames past the length with zeros
+  float* dw;                      // [D]
+  float* ws;                      // >= B * nsb * D floats: per-block partials of dw
+  long long ws_floats;
+  long long st, sb, dst, dsb;
+  int T, B, D, bf16_x;
+};
+void attn_pool_bwd_launch(const AttnBwdArgs& a, hipStream_t st);

@@ -13,6 +13,10 @@ PyTorch-ROCm (MIOpen RNN); ``'native'`` runs the recurrence in the HIP step kern
 input or a hidden size the kernels do not tile; ``'auto'`` takes the native cell only at the
 (batch, hidden) sizes where it was measured not slower (``ops.lstm.MEASURED_NATIVE``).  The
 parameters are the ``nn.LSTM`` modules' own in every case.
+
+``attn`` picks how the two attention poolings run, in the same three values (``Attention``'s
+``impl``): the eager torch chain (default), the HIP kernels of ``csrc/attn.hip``, or those only at
+the shapes where they were measured not slower (``ops.attention.MEASURED_NATIVE``).
 """
 from __future__ import annotations
 
@@ -23,16 +27,47 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
+_IMPLS = ('torch', 'native', 'auto')
+
+
 class Attention(nn.Module):
-    def __init__(self, hidden_size, batch_first=False):
+    """Attention pooling over time: ``(representations [B][D], attentions [B][T])``.
+
+    ``impl='torch'`` (default) is the eager chain below.  ``'native'`` runs the HIP kernels of
+    ``csrc/attn.hip`` (``mercury_amd.ops.attention.attn_pool``): it refuses a CPU input or an
+    unsupported width, and its returned attentions are not differentiable (a caller that
+    differentiates through them keeps ``'torch'``).  ``'auto'`` takes the native path only on the
+    GPU at the shapes in ``ops.attention.MEASURED_NATIVE``.  The parameter is ``att_weights``
+    [1][hidden] in every case."""
+
+    def __init__(self, hidden_size, batch_first=False, impl='torch'):
         super().__init__()
+        if impl not in _IMPLS:
+            raise ValueError("impl must be 'torch', 'native' or 'auto', got %r" % (impl,))
         self.hidden_size = hidden_size
         self.batch_first = batch_first
+        self.impl = impl
         self.att_weights = nn.Parameter(torch.empty(1, hidden_size))
         stdv = 1.0 / math.sqrt(hidden_size)
         nn.init.uniform_(self.att_weights, -stdv, stdv)
 
+    def _native(self, inputs):
+        if self.impl == 'torch':
+            return None
+        from ..ops import attention as native
+        if self.impl == 'auto':
+            if not inputs.is_cuda or inputs.dim() != 3:
+                return None
+            B, T = inputs.shape[:2] if self.batch_first else inputs.shape[1::-1]
+            if (B, T, inputs.shape[2], inputs.dtype) not in native.MEASURED_NATIVE:
+                return None
+        return native
+
     def forward(self, inputs, lengths=None):
+        native = self._native(inputs)
+        if native is not None:
+            x = inputs.transpose(0, 1) if self.batch_first else inputs      # time-major view
+            return native.attn_pool(x, self.att_weights, lengths)
         if not self.batch_first:
             inputs = inputs.transpose(0, 1)
         batch_size, max_len = inputs.shape[:2]
@@ -49,16 +84,19 @@ class Attention(nn.Module):
 
 class MyLSTM(nn.Module):
     def __init__(self, feature_dim, num_classes, hidden_dim=512, lstm_layer=2, dropout=0.2,
-                 cell='torch'):
+                 cell='torch', attn='torch'):
         super().__init__()
         if cell not in ('torch', 'native', 'auto'):
             raise ValueError("cell must be 'torch', 'native' or 'auto', got %r" % (cell,))
+        if attn not in _IMPLS:
+            raise ValueError("attn must be 'torch', 'native' or 'auto', got %r" % (attn,))
         self.cell = cell
+        self.attn = attn
         self.dropout = nn.Dropout(p=dropout)
         self.lstm1 = nn.LSTM(feature_dim, hidden_dim, num_layers=1, bidirectional=True)
-        self.atten1 = Attention(hidden_dim * 2, batch_first=True)
+        self.atten1 = Attention(hidden_dim * 2, batch_first=True, impl=attn)
         self.lstm2 = nn.LSTM(hidden_dim * 2, hidden_dim, num_layers=1, bidirectional=True)
-        self.atten2 = Attention(hidden_dim * 2, batch_first=True)
+        self.atten2 = Attention(hidden_dim * 2, batch_first=True, impl=attn)
         width = hidden_dim * lstm_layer * 2
         self.fc1 = nn.Sequential(nn.Linear(width, width), nn.BatchNorm1d(width), nn.ReLU())
         self.fc2 = nn.Linear(width, num_classes)

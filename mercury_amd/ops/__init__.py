@@ -118,6 +118,7 @@ from .misc import (quantize, pool2d_fwd, maxpool2d_bwd, dwconv_fwd, dwconv_dgrad
                    nchw_to_nhwc8, tern_pack, tern_unpack)
 from .lstm import (lstm_step_fwd, lstm_step_bwd, pack_lstm, BiLSTMFunction, bilstm, emulate,  # noqa: E402
                    MEASURED_NATIVE)
+from .attention import attn_pool_fwd, attn_pool_bwd, AttnPoolFunction, attn_pool  # noqa: E402
 
 __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_fwd', 'pwconv_fwd', 'stem_fwd', 'conv_dgrad', 'conv_wgrad', 'conv_bwd', 'pick_tiles',
            'pack_conv_weight', 'to_nhwc', 'from_nhwc', 'bn_apply', 'bn_bwd', 'BnRunTable', 'sums_numel', 'sums_total', 'streaming_stores',
@@ -126,4 +127,5 @@ __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_f
            'dwconv_fwd', 'dwconv_dgrad', 'dwconv_wgrad', 'dwconv_wgrad_slab_floats',
            'dwconv_bwd', 'dwconv_wgrad_reduce_batch', 'dwconv_wgrad_blocks',
            'nchw_to_nhwc8', 'lstm_step_fwd', 'lstm_step_bwd', 'pack_lstm', 'BiLSTMFunction', 'bilstm',
-           'emulate', 'MEASURED_NATIVE']
+           'emulate', 'MEASURED_NATIVE', 'attn_pool_fwd', 'attn_pool_bwd', 'AttnPoolFunction',
+           'attn_pool']
