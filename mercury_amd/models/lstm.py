@@ -17,6 +17,19 @@ parameters are the ``nn.LSTM`` modules' own in every case.
 ``attn`` picks how the two attention poolings run, in the same three values (``Attention``'s
 ``impl``): the eager torch chain (default), the HIP kernels of ``csrc/attn.hip``, or those only at
 the shapes where they were measured not slower (``ops.attention.MEASURED_NATIVE``).
+
+``packed`` decides whether the two recurrent layers honour ``lengths``.  ``packed=True`` is the
+reference's intended model, a packed-sequence model: each layer computes what
+``pad_packed_sequence(lstm(pack_padded_sequence(x, lengths, enforce_sorted=False)),
+total_length=T)`` computes -- the reverse direction of row b starts at ``t = len_b - 1`` from a
+zero state, the layer output is exactly 0 at ``t >= len_b``, and padded frames reach no
+gradient.  ``cell='torch'`` does it with pack / ``nn.LSTM`` / unpack.  The native cell has no
+variable-length form yet: the step kernels of ``csrc/lstm.hip`` take no lengths, so
+``cell='native'`` with ``packed=True`` and ``lengths`` given is a ``NotImplementedError`` (never a
+silent walk through the padding, never a silent switch to torch), and ``cell='auto'``, which takes
+the native cell only where it was measured, takes the torch cell there.  ``packed=False``
+(default) is the historical behaviour: ``lengths`` reaches only the two attention poolings and
+both recurrences run over the padding.  With ``lengths=None`` the two are the same.
 """
 from __future__ import annotations
 
@@ -84,14 +97,17 @@ class Attention(nn.Module):
 
 class MyLSTM(nn.Module):
     def __init__(self, feature_dim, num_classes, hidden_dim=512, lstm_layer=2, dropout=0.2,
-                 cell='torch', attn='torch'):
+                 cell='torch', attn='torch', packed=False):
         super().__init__()
         if cell not in ('torch', 'native', 'auto'):
             raise ValueError("cell must be 'torch', 'native' or 'auto', got %r" % (cell,))
         if attn not in _IMPLS:
             raise ValueError("attn must be 'torch', 'native' or 'auto', got %r" % (attn,))
+        if not isinstance(packed, bool):
+            raise TypeError('packed must be a bool, got %s' % type(packed).__name__)
         self.cell = cell
         self.attn = attn
+        self.packed = packed
         self.dropout = nn.Dropout(p=dropout)
         self.lstm1 = nn.LSTM(feature_dim, hidden_dim, num_layers=1, bidirectional=True)
         self.atten1 = Attention(hidden_dim * 2, batch_first=True, impl=attn)
@@ -101,9 +117,28 @@ class MyLSTM(nn.Module):
         self.fc1 = nn.Sequential(nn.Linear(width, width), nn.BatchNorm1d(width), nn.ReLU())
         self.fc2 = nn.Linear(width, num_classes)
 
-    def _layer(self, lstm, x):
-        if self.cell == 'torch':
+    @staticmethod
+    def _torch_layer(lstm, x, lengths):
+        if lengths is None:
             return lstm(x)[0]
+        T = x.shape[0]
+        # pack_padded_sequence wants CPU lengths in [1, T]; a row of length 0 is not packable
+        cpu = torch.as_tensor(lengths).detach().to('cpu', torch.int64).clamp(max=T)
+        packed = nn.utils.rnn.pack_padded_sequence(x, cpu, enforce_sorted=False)
+        return nn.utils.rnn.pad_packed_sequence(lstm(packed)[0], total_length=T)[0]
+
+    def _layer(self, lstm, x, lengths=None):
+        if not self.packed:
+            lengths = None
+        if self.cell == 'torch':
+            return self._torch_layer(lstm, x, lengths)
+        if lengths is not None:
+            # the step kernels take no lengths: nothing was measured for 'auto' to follow, and
+            # 'native' has no kernel to run
+            if self.cell == 'auto':
+                return self._torch_layer(lstm, x, lengths)
+            raise NotImplementedError("MyLSTM(packed=True, cell='native'): the native LSTM cell "
+                                      "does not take lengths; use cell='torch' or 'auto'")
         from ..ops import lstm as native
         if self.cell == 'auto' and not (
                 x.is_cuda and (x.shape[1], lstm.hidden_size) in native.MEASURED_NATIVE):
@@ -115,9 +150,9 @@ class MyLSTM(nn.Module):
         if x.dim() == 4:
             x = x.squeeze(1)
         x = x.permute(2, 0, 1)
-        out1 = self._layer(self.lstm1, x)
+        out1 = self._layer(self.lstm1, x, lengths)
         a, _ = self.atten1(out1.transpose(0, 1), lengths)
-        out2 = self._layer(self.lstm2, out1)
+        out2 = self._layer(self.lstm2, out1, lengths)
         b, _ = self.atten2(out2.transpose(0, 1), lengths)
         z = torch.cat([a, b], dim=1)
         z = self.fc1(self.dropout(z))
