@@ -63,10 +63,21 @@ def maxpool2d_bwd(dy, argmax, dx, N, H, W, C, P, Q, k, stride, pad):
 _ACT = {None: 0, 'none': 0, 'relu': 1, 'relu6': 2}
 
 
+def _dw_chk(name, C, bw=None):
+    """The depthwise kernels walk C in 16-byte chunks of 8 channels (a remainder would be left
+    unwritten), and the fused BN-backward fold needs a block to hold whole periods of C / 8
+    chunks (C / 8 <= 256 threads)."""
+    if C < 8 or C % 8:
+        raise ValueError('%s: C must be a positive multiple of 8, got %d' % (name, C))
+    if bw is not None and C > 2048:
+        raise ValueError('%s: bw= needs C <= 2048, got %d' % (name, C))
+
+
 def dwconv_fwd(x, w, y, N, H, W, C, P, Q, stride, pad, stats=None, group_rows=0, pro=None):
     """Depthwise 3x3 forward (+ BN sums).  ``pro``: x is the producer's raw output and
     act(bn(x)) is applied to each loaded chunk -- dict(stats=[G][2][C] | rmean/rvar, gamma,
     beta, act, eps, count, group_imgs, keep=optional activation output)."""
+    _dw_chk('dwconv_fwd', C)
     pa = (0, 0, 0, 0, 0, 0, 0.0, 0.0, 0, 0)
     if pro is not None:
         for k in ('stats', 'rmean', 'rvar', 'gamma', 'beta'):
@@ -86,6 +97,7 @@ def dwconv_dgrad(dy, w, dx, N, H, W, C, P, Q, stride, pad, bw=None):
     """Depthwise 3x3 data gradient.  ``bw``: dict(out=, y=, stats=[2][C], sums=[SUMS_R][3][C], act=,
     eps=) -- also reduce the BN-backward sums of the BN feeding this conv (its activation
     ``out``, input ``y``), as bn_bwd's reduce pass would (one batch group)."""
+    _dw_chk('dwconv_dgrad', C, bw)
     ba = (0, 0, 0, 0, 0.0, 0.0, 0)
     if bw is not None:
         n_in = N * H * W * C
@@ -104,6 +116,7 @@ def dwconv_bwd(dy, x, w, dx, dw, N, H, W, C, P, Q, stride, pad, slab, bw=None, r
     """Depthwise dgrad (+ fused BN-backward sums ``bw``, as dwconv_dgrad) and slab wgrad in
     ONE launch.  ``slab`` (fp32, >= dwconv_wgrad_slab_floats): the wgrad blocks' partials;
     ``reduce=False`` leaves them for dwconv_wgrad_reduce_batch (dw is then not yet updated)."""
+    _dw_chk('dwconv_bwd', C, bw)
     _chk(slab, torch.float32, 'slab', dwconv_wgrad_slab_floats(N, P, Q, C))
     _chk(dy, torch.bfloat16, 'dy', N * P * Q * C)
     ba = (0, 0, 0, 0, 0.0, 0.0, 0)
@@ -146,6 +159,7 @@ def dwconv_wgrad(dy, x, dw, N, H, W, C, P, Q, stride, pad, slab=None):
     """dw[C][9] += depthwise 3x3 weight gradient.  ``slab`` (fp32, >= dwconv_wgrad_slab_floats
     elements): column-segmented rows with the blocks' partials summed by a second kernel
     instead of atomics (faster at the train batch)."""
+    _dw_chk('dwconv_wgrad', C)
     _chk(slab, torch.float32, 'slab')
     lib().dwconv_wgrad(ptr(dy), ptr(x), ptr(dw), N, H, W, C, P, Q, stride, pad, stream_ptr(),
                        ptr(slab), 0 if slab is None else slab.numel())
