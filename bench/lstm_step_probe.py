@@ -11,6 +11,10 @@ backward-grouping figures quoted in csrc/lstm.hip and the README:
 
 ``--gemm`` also times the forms of the time-batched pre GEMM x . W_ih^T (bf16 operands with an
 fp32 result, fp32 operands, bf16 result) and the [T][B][2][4H] -> [T][2][B][4H] copy.
+``--lengths full`` / ``uniform`` times the kernels with a device lengths tensor: all rows of
+length T, or lengths uniform in [T/2, T] (``--seed``); ``uniform`` also times the launches cut
+to max(len_b) steps, as host-side lengths run them (still divided by T).  A build with
+``-DLSTM_NO_WAVE_SKIP`` keeps all-padded waves in the K loop, for what the skip buys.
 One JSON line per run, appended to ``--out``.
 """
 from __future__ import annotations
@@ -30,14 +34,25 @@ def main():
     ap.add_argument('--label', default='shipped')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r8', 'lstm', 'step_probe.jsonl'))
     ap.add_argument('--gemm', action='store_true')
+    ap.add_argument('--lengths', choices=('none', 'full', 'uniform'), default='none')
+    ap.add_argument('--seed', type=int, default=0)
     args = ap.parse_args()
     import torch
     from gtime import gtime
     from mercury_amd.ops import lstm as L
     T, H = 161, 512
     bf = torch.bfloat16
-    res = {'label': args.label, 'T': T, 'H': H, 'unit': 'us per step (graph replay of T steps / T)'}
+    res = {'label': args.label, 'T': T, 'H': H, 'unit': 'us per step (graph replay of T steps / T)',
+           'lengths': args.lengths}
     for B in (32, 320):
+        kw, Te = {}, T
+        if args.lengths != 'none':
+            g = torch.Generator().manual_seed(args.seed)
+            lens = (torch.full((B,), T) if args.lengths == 'full'
+                    else torch.randint(T // 2, T + 1, (B,), generator=g))
+            kw = {'lengths': lens.to('cuda', torch.int32)}
+            Te = int(lens.max())
+            res['max_len_B%d' % B], res['mean_len_B%d' % B] = Te, round(float(lens.float().mean()), 1)
         pre = torch.randn(T, 2, B, 4 * H, device='cuda')
         whh = (torch.randn(2, 4 * H, H, device='cuda') / H ** 0.5).to(bf)
         whhT = whh.transpose(1, 2).contiguous()
@@ -48,9 +63,14 @@ def main():
         dout = torch.randn(T, B, 2 * H, device='cuda')
         dG = torch.empty_like(gates)
         dc = torch.empty(2, B, H, device='cuda')
-        runs = {'fwd_train': lambda: L.lstm_step_fwd(pre, whh, out, c, gates, T=T, B=B, H=H),
-                'fwd_infer': lambda: L.lstm_step_fwd(pre, whh, out, c1, None, T=T, B=B, H=H),
-                'bwd': lambda: L.lstm_step_bwd(dout, gates, c, whhT, dG, dc, T=T, B=B, H=H)}
+        runs = {'fwd_train': lambda: L.lstm_step_fwd(pre, whh, out, c, gates, T=T, B=B, H=H, **kw),
+                'fwd_infer': lambda: L.lstm_step_fwd(pre, whh, out, c1, None, T=T, B=B, H=H, **kw),
+                'bwd': lambda: L.lstm_step_bwd(dout, gates, c, whhT, dG, dc, T=T, B=B, H=H, **kw)}
+        if Te < T:
+            runs.update({
+                'fwd_train_trim': lambda: L.lstm_step_fwd(pre, whh, out, c, gates, T=Te, B=B, H=H, **kw),
+                'fwd_infer_trim': lambda: L.lstm_step_fwd(pre, whh, out, c1, None, T=Te, B=B, H=H, **kw),
+                'bwd_trim': lambda: L.lstm_step_bwd(dout, gates, c, whhT, dG, dc, T=Te, B=B, H=H, **kw)})
         for k, fn in runs.items():
             res['%s_B%d' % (k, B)] = round(gtime(fn, reps=2, iters=5) / T, 2)
         if args.gemm:

@@ -532,18 +532,20 @@ PYBIND11_MODULE(_C, m) {
 
   // BiLSTM recurrence (lstm.hip): steps [s0, s1) of a sequence, one launch per step
   m.def("lstm_step_fwd", [](uintptr_t pre, uintptr_t whh, uintptr_t out, uintptr_t c,
-                            uintptr_t gates, uintptr_t h0, uintptr_t c0, int T, int B, int H,
-                            int s0, int s1, int train, uintptr_t st) {
+                            uintptr_t gates, uintptr_t h0, uintptr_t c0, uintptr_t lens, int T,
+                            int B, int H, int s0, int s1, int train, uintptr_t st) {
     LstmFwdArgs a{P<const float>(pre), P<const bf16>(whh), P<bf16>(out), P<float>(c),
-                  P<bf16>(gates), P<const bf16>(h0), P<const float>(c0), T, B, H, 0, train};
+                  P<bf16>(gates), P<const bf16>(h0), P<const float>(c0), T, B, H, 0, train,
+                  P<const int>(lens)};
     for (a.s = s0; a.s < s1; ++a.s) lstm_step_fwd_launch(a, S(st));
     check_launch("lstm_step_fwd");
   });
   m.def("lstm_step_bwd", [](uintptr_t dout, uintptr_t gates, uintptr_t c, uintptr_t whhT,
-                            uintptr_t dG, uintptr_t dc, int T, int B, int H, int s0, int s1,
-                            uintptr_t st) {
+                            uintptr_t dG, uintptr_t dc, uintptr_t lens, int T, int B, int H,
+                            int s0, int s1, uintptr_t st) {
     LstmBwdArgs a{P<const float>(dout), P<const bf16>(gates), P<const float>(c),
-                  P<const bf16>(whhT), P<bf16>(dG), P<float>(dc), T, B, H, 0};
+                  P<const bf16>(whhT), P<bf16>(dG), P<float>(dc), T, B, H, 0,
+                  P<const int>(lens)};
     for (a.s = s0; a.s < s1; ++a.s) lstm_step_bwd_launch(a, S(st));
     check_launch("lstm_step_bwd");
   });

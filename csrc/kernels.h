@@ -359,6 +359,8 @@ struct LstmFwdArgs {
   const bf16* h0;                 // [2][B][H] initial state, or null = zero
   const float* c0;                // [2][B][H], or null = zero
   int T, B, H, s, train;
+  const int* lens = nullptr;      // [B] or null: frame (t, b) is valid iff t < clamp(lens[b], 0, T);
+                                  // padded frames get h = +0 and c = 0.  Not with h0 / c0.
 };
 void lstm_step_fwd_launch(const LstmFwdArgs& a, hipStream_t st);
 struct LstmBwdArgs {                // of a forward that started from a zero state
@@ -369,6 +371,7 @@ struct LstmBwdArgs {                // of a forward that started from a zero sta
   bf16* dG;                       // [T][2][B][4H] pre-activation gradients; step s reads step s-1's
   float* dc;                      // [2][B][H] dc_next in, dc_prev out (in place); step 0 reads zero
   int T, B, H, s;
+  const int* lens = nullptr;      // as the forward's; padded frames get dG[t] = 0 and dc = 0
 };
 void lstm_step_bwd_launch(const LstmBwdArgs& a, hipStream_t st);
 // attention pooling over time (attn.hip): s = x . w, a = masked softmax_t(relu(s)),

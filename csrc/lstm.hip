@@ -18,6 +18,17 @@
 // lane's 16-byte load is exactly its MFMA fragment.  One wave per block: 16 units x 16 * MB batch
 // rows; rows past B read row B-1 (their MFMA columns are independent) and are never stored.
 // No atomics: every output element has one writer, so two runs are bit-equal.
+//
+// Lengths (the <.., true> instantiations, args.lens != null): frame (t, b) is valid iff
+// t < len_b = clamp(lens[b], 0, T) -- packed-sequence semantics by per-row masking.  A lane whose
+// row is padded at this step's t reads none of pre / dout / gates and stores exact zeros: h = +0
+// and c = 0 in the forward, dG[t] = 0 and dc = 0 in the backward (a select by branch, never a
+// multiply, so a NaN in the padding reaches nothing).  That alone makes both directions right:
+// the reverse pass of row b first becomes valid at t = len_b - 1 and finds the zero h and c an
+// earlier launch stored at len_b; the backward's first valid step finds dG[len_b] = 0 and dc = 0.
+// A wave whose rows are all padded at this step (rows past B count as padded) skips the K loop:
+// no weight, h_prev or dG loads, only its zero stores.  Without lens the kernels are the
+// <.., false> instantiations: the code they were before lengths existed.
 #include <stdexcept>
 #include <string>
 
@@ -70,7 +81,25 @@ MA_DEV void bwd_chunks(const bf16* w, const bf16* const (&grow)[MB], int k0, f32
       acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fg[j][m], acc[m], 0, 0, 0);
 }
 
+// valid[m]: this lane's row of tile m is a real row and t is inside its sequence; returns whether
+// any lane of the wave has a valid row in any tile (wave-uniform)
 template <int MB>
+MA_DEV bool row_valid(const int* lens, int T, int B, int t, int b0, int lane, bool (&valid)[MB]) {
+  bool any = false;
+#pragma unroll
+  for (int m = 0; m < MB; ++m) {
+    const int b = b0 + 16 * m + (lane & 15);
+    valid[m] = b < B && t < min(max(lens[min(b, B - 1)], 0), T);
+    any |= valid[m];
+  }
+#ifdef LSTM_NO_WAVE_SKIP
+  return true;                         // A/B builds only: what skipping all-padded waves buys
+#else
+  return __ballot(any) != 0;
+#endif
+}
+
+template <int MB, bool LENS>
 __global__ __launch_bounds__(64) void lstm_step_fwd_kernel(LstmFwdArgs a) {
   const int lane = threadIdx.x, d = blockIdx.z;
   const int H = a.H, B = a.B;
@@ -81,6 +110,8 @@ __global__ __launch_bounds__(64) void lstm_step_fwd_kernel(LstmFwdArgs a) {
   const bf16* hp = first ? (a.h0 ? a.h0 + (size_t)d * B * H : nullptr)
                          : a.out + (size_t)tp * B * 2 * H + (size_t)d * H;
   const int ldh = first ? H : 2 * H;
+  bool valid[MB], work = true;
+  if constexpr (LENS) work = row_valid<MB>(a.lens, a.T, B, t, b0, lane, valid);
 
   f32x4 acc[MB][4];
 #pragma unroll
@@ -88,7 +119,7 @@ __global__ __launch_bounds__(64) void lstm_step_fwd_kernel(LstmFwdArgs a) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) acc[m][g] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  if (hp) {
+  if (hp && work) {
     const int kq = 8 * (lane >> 4);
     const bf16* wrow = a.whh + ((size_t)d * 4 * H + u0 + (lane & 15)) * H + kq;
     const bf16* hrow[MB];
@@ -119,6 +150,13 @@ __global__ __launch_bounds__(64) void lstm_step_fwd_kernel(LstmFwdArgs a) {
   for (int m = 0; m < MB; ++m) {
     const int b = b0 + 16 * m + (lane & 15);
     if (b >= B) continue;
+    if constexpr (LENS) {
+      if (!valid[m]) {               // padded frame: h = +0, c = 0, pre not read, gates not written
+        *(f32x4*)(cout + (size_t)b * H + u) = f32x4{0.f, 0.f, 0.f, 0.f};
+        *(short4v*)(a.out + ((size_t)t * B + b) * 2 * H + (size_t)d * H + u) = short4v{0, 0, 0, 0};
+        continue;
+      }
+    }
     const size_t grow = ((size_t)(t * 2 + d) * B + b) * 4 * H + u;
     f32x4 gt[4];
 #pragma unroll
@@ -144,7 +182,7 @@ __global__ __launch_bounds__(64) void lstm_step_fwd_kernel(LstmFwdArgs a) {
   }
 }
 
-template <int MB>
+template <int MB, bool LENS>
 __global__ __launch_bounds__(64) void lstm_step_bwd_kernel(LstmBwdArgs a) {
   const int lane = threadIdx.x, d = blockIdx.z;
   const int H = a.H, B = a.B;
@@ -153,12 +191,14 @@ __global__ __launch_bounds__(64) void lstm_step_bwd_kernel(LstmBwdArgs a) {
   const int tn = d ? t - 1 : t + 1;      // the step the previous launch wrote dG for
   const int tc = d ? t + 1 : t - 1;      // the step whose c is this step's c_prev
   const bool first = a.s == 0, last = a.s == a.T - 1;
+  bool valid[MB], work = true;
+  if constexpr (LENS) work = row_valid<MB>(a.lens, a.T, B, t, b0, lane, valid);
 
   f32x4 acc[MB];
 #pragma unroll
   for (int m = 0; m < MB; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  if (!first) {    // dh_rec = dG[tn] . W_hh, K = 4H over the rows of W_hh^T
+  if (!first && work) {    // dh_rec = dG[tn] . W_hh, K = 4H over the rows of W_hh^T
     const int kq = 8 * (lane >> 4);
     const int K = 4 * H;
     const bf16* wrow = a.whhT + ((size_t)d * H + u0 + (lane & 15)) * K + kq;
@@ -179,6 +219,15 @@ __global__ __launch_bounds__(64) void lstm_step_bwd_kernel(LstmBwdArgs a) {
   for (int m = 0; m < MB; ++m) {
     const int b = b0 + 16 * m + (lane & 15);
     if (b >= B) continue;
+    if constexpr (LENS) {
+      if (!valid[m]) {               // padded frame: dG[t] = 0, dc = 0, dout and gates not read
+        bf16* z = a.dG + ((size_t)(t * 2 + d) * B + b) * 4 * H + u;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) *(short4v*)(z + (size_t)g * H) = short4v{0, 0, 0, 0};
+        *(f32x4*)(a.dc + cd + (size_t)b * H + u) = f32x4{0.f, 0.f, 0.f, 0.f};
+        continue;
+      }
+    }
     const size_t grow = ((size_t)(t * 2 + d) * B + b) * 4 * H + u;
     const f32x4 dh = ldf4(a.dout + ((size_t)t * B + b) * 2 * H + (size_t)d * H + u) + acc[m];
     const f32x4 gi = ldb4(a.gates + grow), gf = ldb4(a.gates + grow + H),
@@ -232,10 +281,17 @@ void lstm_step_fwd_launch(const LstmFwdArgs& a, hipStream_t st) {
   check_shape("lstm_step_fwd", a.T, a.B, a.H, a.s);
   if (!a.pre || !a.whh || !a.out || !a.c || (a.train && !a.gates))
     throw std::invalid_argument("lstm_step_fwd: null operand");
+  if (a.lens && (a.h0 || a.c0))
+    throw std::invalid_argument("lstm_step_fwd: lens with h0 / c0 is not supported");
   const int mb = tiles_per_wave(a.B);
   const dim3 grid(a.H / 16, (a.B + 16 * mb - 1) / (16 * mb), 2);
-  if (mb == 1) lstm_step_fwd_kernel<1><<<grid, 64, 0, st>>>(a);
-  else lstm_step_fwd_kernel<2><<<grid, 64, 0, st>>>(a);
+  if (a.lens) {
+    if (mb == 1) lstm_step_fwd_kernel<1, true><<<grid, 64, 0, st>>>(a);
+    else lstm_step_fwd_kernel<2, true><<<grid, 64, 0, st>>>(a);
+  } else {
+    if (mb == 1) lstm_step_fwd_kernel<1, false><<<grid, 64, 0, st>>>(a);
+    else lstm_step_fwd_kernel<2, false><<<grid, 64, 0, st>>>(a);
+  }
   HIP_LAUNCH_CHECK();
 }
 
@@ -245,7 +301,12 @@ void lstm_step_bwd_launch(const LstmBwdArgs& a, hipStream_t st) {
     throw std::invalid_argument("lstm_step_bwd: null operand");
   const int mb = tiles_per_wave(a.B);
   const dim3 grid(a.H / 16, (a.B + 16 * mb - 1) / (16 * mb), 2);
-  if (mb == 1) lstm_step_bwd_kernel<1><<<grid, 64, 0, st>>>(a);
-  else lstm_step_bwd_kernel<2><<<grid, 64, 0, st>>>(a);
+  if (a.lens) {
+    if (mb == 1) lstm_step_bwd_kernel<1, true><<<grid, 64, 0, st>>>(a);
+    else lstm_step_bwd_kernel<2, true><<<grid, 64, 0, st>>>(a);
+  } else {
+    if (mb == 1) lstm_step_bwd_kernel<1, false><<<grid, 64, 0, st>>>(a);
+    else lstm_step_bwd_kernel<2, false><<<grid, 64, 0, st>>>(a);
+  }
   HIP_LAUNCH_CHECK();
 }

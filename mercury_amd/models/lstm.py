@@ -23,11 +23,12 @@ reference's intended model, a packed-sequence model: each layer computes what
 ``pad_packed_sequence(lstm(pack_padded_sequence(x, lengths, enforce_sorted=False)),
 total_length=T)`` computes -- the reverse direction of row b starts at ``t = len_b - 1`` from a
 zero state, the layer output is exactly 0 at ``t >= len_b``, and padded frames reach no
-gradient.  ``cell='torch'`` does it with pack / ``nn.LSTM`` / unpack.  The native cell has no
-variable-length form yet: the step kernels of ``csrc/lstm.hip`` take no lengths, so
-``cell='native'`` with ``packed=True`` and ``lengths`` given is a ``NotImplementedError`` (never a
-silent walk through the padding, never a silent switch to torch), and ``cell='auto'``, which takes
-the native cell only where it was measured, takes the torch cell there.  ``packed=False``
+gradient.  ``cell='torch'`` does it with pack / ``nn.LSTM`` / unpack.  ``cell='native'`` does it
+in the step kernels of ``csrc/lstm.hip``, which take device lengths and mask per row
+(``ops.lstm.bilstm(x, lstm, lengths)``: no packing, no host synchronisation); on an input that is
+not on a HIP device it is a ``NotImplementedError`` (never a silent walk through the padding,
+never a silent switch to torch).  ``cell='auto'`` with lengths takes the native cell only on the
+GPU at the (batch, hidden) sizes in ``ops.lstm.MEASURED_NATIVE_PACKED`` and torch elsewhere.  ``packed=False``
 (default) is the historical behaviour: ``lengths`` reaches only the two attention poolings and
 both recurrences run over the padding.  With ``lengths=None`` the two are the same.
 """
@@ -132,14 +133,17 @@ class MyLSTM(nn.Module):
             lengths = None
         if self.cell == 'torch':
             return self._torch_layer(lstm, x, lengths)
-        if lengths is not None:
-            # the step kernels take no lengths: nothing was measured for 'auto' to follow, and
-            # 'native' has no kernel to run
-            if self.cell == 'auto':
-                return self._torch_layer(lstm, x, lengths)
-            raise NotImplementedError("MyLSTM(packed=True, cell='native'): the native LSTM cell "
-                                      "does not take lengths; use cell='torch' or 'auto'")
         from ..ops import lstm as native
+        if lengths is not None:
+            if self.cell == 'auto':
+                if not (x.is_cuda and
+                        (x.shape[1], lstm.hidden_size) in native.MEASURED_NATIVE_PACKED):
+                    return self._torch_layer(lstm, x, lengths)
+            elif not x.is_cuda:
+                raise NotImplementedError("MyLSTM(packed=True, cell='native'): the native LSTM "
+                                          "cell takes lengths only on a HIP device; use "
+                                          "cell='torch' or 'auto'")
+            return native.bilstm(x, lstm, lengths)
         if self.cell == 'auto' and not (
                 x.is_cuda and (x.shape[1], lstm.hidden_size) in native.MEASURED_NATIVE):
             return lstm(x)[0]

@@ -117,7 +117,7 @@ from .misc import (quantize, pool2d_fwd, maxpool2d_bwd, dwconv_fwd, dwconv_dgrad
                    dwconv_bwd, dwconv_wgrad_reduce_batch, dwconv_wgrad_blocks,  # noqa: E402
                    nchw_to_nhwc8, tern_pack, tern_unpack)
 from .lstm import (lstm_step_fwd, lstm_step_bwd, pack_lstm, BiLSTMFunction, bilstm, emulate,  # noqa: E402
-                   MEASURED_NATIVE)
+                   MEASURED_NATIVE, MEASURED_NATIVE_PACKED)
 from .attention import attn_pool_fwd, attn_pool_bwd, AttnPoolFunction, attn_pool  # noqa: E402
 
 __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_fwd', 'pwconv_fwd', 'stem_fwd', 'conv_dgrad', 'conv_wgrad', 'conv_bwd', 'pick_tiles',
