@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "grad_norm_plan.h"
 #include "kernels.h"
 
 int igemm_read_stamps(unsigned long long* host, int n);
@@ -686,21 +687,34 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("optimizer", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t segs,
                         int nsegs, long long total, uintptr_t hyper, uintptr_t step, int algo,
-                        int zero_grad, uintptr_t st, long long start) {
+                        int zero_grad, uintptr_t st, long long start, uintptr_t gscale) {
     OptArgs a{P<float>(p), P<float>(g), P<float>(mm), P<float>(v), P<const OptSeg>(segs), nsegs,
-              total, P<const float>(hyper), P<const int64_t>(step), algo, zero_grad, start};
+              total, P<const float>(hyper), P<const int64_t>(step), algo, zero_grad, start,
+              P<const float>(gscale)};
     optimizer_launch(a, S(st));
     check_launch("optimizer");
   });
   m.def("optimizer_fused", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t segs,
                               int nsegs, long long total, uintptr_t hyper, uintptr_t step,
                               int algo, int zero_grad, uintptr_t jobs, int njobs, uintptr_t ew,
-                              uintptr_t ewp, int new_, long long ew4, uintptr_t st) {
+                              uintptr_t ewp, int new_, long long ew4, uintptr_t st,
+                              uintptr_t gscale) {
     OptArgs a{P<float>(p), P<float>(g), P<float>(mm), P<float>(v), P<const OptSeg>(segs), nsegs,
-              total, P<const float>(hyper), P<const int64_t>(step), algo, zero_grad, 0};
+              total, P<const float>(hyper), P<const int64_t>(step), algo, zero_grad, 0,
+              P<const float>(gscale)};
     optimizer_fused_launch(a, P<const int>(jobs), njobs, P<const long long>(ew),
                            P<const long long>(ewp), new_, ew4, S(st));
     check_launch("optimizer_fused");
+  });
+  m.def("grad_norm", [](uintptr_t g, long long n, uintptr_t max_norm, uintptr_t rec, uintptr_t ws,
+                        long long ws_floats, uintptr_t st) {
+    grad_norm_launch(P<const float>(g), n, P<const float>(max_norm), P<float>(rec), P<float>(ws),
+                     ws_floats, S(st));
+    check_launch("grad_norm");
+  });
+  m.def("grad_norm_plan", [](long long n) {
+    const GradNormPlan p = grad_norm_plan(n);
+    return py::make_tuple(p.n4, p.tail, p.blocks, p.trips, GN_NT, GN_U, GN_CAP);
   });
   m.def("pack_weights", [](uintptr_t p, uintptr_t segs, int nsegs, long long total, uintptr_t st) {
     pack_weights_launch(P<const float>(p), P<const OptSeg>(segs), nsegs, total, S(st));

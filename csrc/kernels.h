@@ -248,7 +248,16 @@ struct OptArgs {
   int algo;                      // 0 adam (L2 in the gradient), 1 sgd(momentum), 2 adamw
   int zero_grad;
   long long start;               // first element of the swept range (4-aligned segment start)
+  const float* gscale;           // device clip coefficient the gradient is multiplied by before
+                                 // weight decay (grad_norm_launch's record[1]); null: no clipping
 };
+// L2 norm of g[0, n) and the clip coefficient min(1, *max_norm / (norm + 1e-6)) into
+// rec[0], rec[1] (torch.nn.utils.clip_grad_norm_, error_if_nonfinite=False).  Two launches on
+// `st`: per-block fp32 partial sums of squares into ws[0, plan.blocks), then one block that
+// combines them in fp64.  Fixed summation order, no atomics: bit-equal from run to run.
+// Throws std::invalid_argument (grad_norm_plan.h grad_norm_check); allocates and syncs nothing.
+void grad_norm_launch(const float* g, long long n, const float* max_norm, float* rec, float* ws,
+                      long long ws_floats, hipStream_t st);
 void optimizer_launch(const OptArgs& a, hipStream_t st);
 // full step in one launch: tile jobs (conv segments with a dgrad copy, C % 4 == 0) write both
 // bf16 copies; ew ([n][2] start, numel) / ewp ([n+1] float4 prefix) cover everything else

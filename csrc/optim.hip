@@ -18,6 +18,7 @@
 // cosine schedule) and the step counter live in device memory so the launch is
 // graph-capturable and replays with the current values.
 #include "common.h"
+#include "grad_norm_plan.h"
 #include "kernels.h"
 
 namespace {
@@ -75,8 +76,8 @@ __global__ __launch_bounds__(256) void transpose_weights_kernel(const OptSeg* se
 // Adam / AdamW / SGD-momentum on 4 consecutive elements (the flat layout keeps segments
 // 4-aligned, so a float4 never straddles two parameters)
 struct OptHyper {
-  float lr, b1, b2, eps, wd, step_size, rbc2;
-  bool first;
+  float lr, b1, b2, eps, wd, step_size, rbc2, gs;
+  bool first, clip;
 };
 
 MA_DEV OptHyper opt_hyper(const OptArgs& a) {
@@ -90,7 +91,17 @@ MA_DEV OptHyper opt_hyper(const OptArgs& a) {
   h.step_size = h.lr / (1.f - __powf(h.b1, t));
   h.rbc2 = rsqrtf(1.f - __powf(h.b2, t));
   h.first = *a.step <= 1;
+  h.clip = a.gscale != nullptr;
+  h.gs = h.clip ? *a.gscale : 1.f;
   return h;
+}
+
+// Global-norm clipping: g * coefficient, rounded to fp32 on its own (never contracted into the
+// weight-decay or momentum FMA that follows), so a clipped step equals an unclipped step on a
+// gradient that was multiplied by the coefficient beforehand, bit for bit.
+MA_DEV float clip_grad(float g, float s) {
+#pragma clang fp contract(off)
+  return g * s;
 }
 
 MA_DEV float4 opt_update4(const OptArgs& a, const OptHyper& h, long long e) {
@@ -98,6 +109,10 @@ MA_DEV float4 opt_update4(const OptArgs& a, const OptHyper& h, long long e) {
   float4 g = *(const float4*)(a.g + e);
   float4 m = *(const float4*)(a.m + e);
   float pv[4] = {p.x, p.y, p.z, p.w}, gv[4] = {g.x, g.y, g.z, g.w}, mv[4] = {m.x, m.y, m.z, m.w};
+  if (h.clip) {                  // clip first, then the step (weight decay sees the clipped g)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) gv[k] = clip_grad(gv[k], h.gs);
+  }
   if (a.algo == 0 || a.algo == 2) {
     float4 v = *(const float4*)(a.v + e);
     float vv[4] = {v.x, v.y, v.z, v.w};
@@ -253,7 +268,87 @@ __global__ __launch_bounds__(256) void step_begin_kernel(int64_t* ctrl, float* z
   for (int j = i; j < n0; j += stride) z0[j] = 0.f;
   for (int j = i; j < n1; j += stride) z1[j] = 0.f;
 }
+
+// ---------------------------------------------------------------- gradient norm
+// Sum of squares of g[0, n): every thread keeps ONE fp32 accumulator over its float4s (GN_U per
+// grid-stride trip, coalesced 4 KB rows per block), block 0's thread 0 adds the n % 4 tail, then a
+// fixed tree (6 shuffle levels, the 4 wave sums in wave order) and one partial per block.  The
+// order depends on (n, grid) only, so two runs on the same data are bit-equal.
+__global__ __launch_bounds__(GN_NT) void grad_sumsq_kernel(const float* __restrict__ g,
+                                                           long long n, float* __restrict__ part) {
+  __shared__ float wsum[GN_NT / 64];
+  const long long n4 = n >> 2;
+  const float4* g4 = (const float4*)g;
+  const long long stride = (long long)gridDim.x * (GN_NT * GN_U);
+  float acc = 0.f;
+  for (long long base = (long long)blockIdx.x * (GN_NT * GN_U); base < n4; base += stride) {
+    float4 x[GN_U];
+#pragma unroll
+    for (int u = 0; u < GN_U; ++u) {
+      const long long i = base + u * GN_NT + threadIdx.x;
+      x[u] = i < n4 ? g4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < GN_U; ++u) {
+      acc = fmaf(x[u].x, x[u].x, acc);
+      acc = fmaf(x[u].y, x[u].y, acc);
+      acc = fmaf(x[u].z, x[u].z, acc);
+      acc = fmaf(x[u].w, x[u].w, acc);
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    for (long long j = n4 * 4; j < n; ++j) acc = fmaf(g[j], g[j], acc);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = wsum[0];
+#pragma unroll
+    for (int w = 1; w < GN_NT / 64; ++w) s += wsum[w];
+    part[blockIdx.x] = s;
+  }
+}
+
+// One block: thread t adds partials [4t, 4t + 4) in index order in fp64, then the same fixed
+// tree; thread 0 writes the record.  A NaN coefficient (NaN norm, or inf / inf) is kept: the
+// comparison below is false for it, as torch.clamp(max=1) keeps it.
+__global__ __launch_bounds__(GN_NT) void grad_norm_finish_kernel(const float* __restrict__ part,
+                                                                 int nparts,
+                                                                 const float* __restrict__ max_norm,
+                                                                 float* __restrict__ rec) {
+  static_assert(GN_CAP <= 4 * GN_NT, "four partials per thread cover the grid cap");
+  __shared__ double wsum[GN_NT / 64];
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = threadIdx.x * 4 + j;
+    if (i < nparts) acc += (double)part[i];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = wsum[0];
+#pragma unroll
+    for (int w = 1; w < GN_NT / 64; ++w) s += wsum[w];
+    const float norm = (float)sqrt(s);
+    const float c = *max_norm / (norm + 1e-6f);
+    rec[0] = norm;
+    rec[1] = c > 1.f ? 1.f : c;
+  }
+}
 }  // namespace
+
+void grad_norm_launch(const float* g, long long n, const float* max_norm, float* rec, float* ws,
+                      long long ws_floats, hipStream_t st) {
+  const GradNormPlan p = grad_norm_check((uintptr_t)g, n, (uintptr_t)max_norm, (uintptr_t)rec,
+                                         (uintptr_t)ws, ws_floats);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(p.blocks), dim3(GN_NT), 0, st, g, n, ws);
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GN_NT), 0, st, (const float*)ws,
+                     p.blocks, max_norm, rec);
+}
 
 void optimizer_launch(const OptArgs& a, hipStream_t st) {
   if (a.total <= a.start) return;

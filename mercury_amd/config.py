@@ -46,6 +46,8 @@ class Config:
     base_lr: float = 0.001          # lr = base_lr * world_size (linear scaling)
     momentum: float = 0.9
     weight_decay: float = 0.0
+    clip_grad_norm: float = 0.0     # clip the gradient's global L2 norm to this before the optimizer
+                                    # step (torch.nn.utils.clip_grad_norm_); 0 = off
     num_epochs: int = 100
     max_samples: int = 10_000_000   # `fit` stops once step*W exceeds this
     seed: int = 102

@@ -134,7 +134,8 @@ class NativeEngine(object):
                  sampler='alias', exchange_scores=False, global_table=True, score='loss',
                  global_ema=False, autotune=None, force_buckets=False, comm='auto',
                  wire_bf16=False, debug=False, check_order=False, grad_compress=None,
-                 opts=None, augment=None, eval_augment=None):
+                 opts=None, augment=None, eval_augment=None, clip_grad_norm=0.0):
+        self.clip_grad_norm = ops.optim.check_max_norm(clip_grad_norm)
         ops.lib()
         _warn_hw_queues()
         from ..config import EngineOptions
@@ -354,7 +355,8 @@ class NativeEngine(object):
                          w_krsc=self.w1p, w_crsk=None)
             segs.append(d)
         self.opt = ops.FlatOptimizer(segs, self.lw.total, self.device, optimizer, lr, betas, eps,
-                                     wd, momentum, fused=self.opts.fused_opt)
+                                     wd, momentum, fused=self.opts.fused_opt,
+                                     clip_grad_norm=self.clip_grad_norm)
         self.load_from_module()
 
     def _pview(self, seg, grad=False):
@@ -1075,6 +1077,10 @@ class NativeEngine(object):
                 self._order(slot=1, ref=3, mult=1, add=1, at=4)
             self._order(tick=3, at=5)
         (self.bn_table if self.scoring else self.bn_table_uniform).launch(0.1)
+        if self.opt.clip_on:
+            # global-norm clipping: the tail runs behind every bucket's all-reduce, so this is
+            # the norm of the averaged gradient and every rank computes the same coefficient
+            self.opt.clip()
         self.opt.step(self.ctrl[2:3])
         self.gather_batch()
 
@@ -1579,7 +1585,7 @@ class NativeTrainer(Trainer):
             score=cfg.score, global_ema=cfg.global_ema, wire_bf16=cfg.wire_bf16,
             grad_compress=cfg.grad_compress,
             comm=cfg.comm, debug=cfg.debug, check_order=cfg.check_order,
-            force_buckets=cfg.force_buckets)
+            force_buckets=cfg.force_buckets, clip_grad_norm=cfg.clip_grad_norm)
         self.engine.set_shard(x, y)
         self.engine.roctx = cfg.roctx
         from ..utils.profiling import StepWindow
@@ -1674,10 +1680,16 @@ class NativeTrainer(Trainer):
                    'opt+tail {tail:.3f}, IS share {share:.1f}%').format(
                        exp=ph.get('comm_exposed', 0.0), share=100.0 * ph['score'] / max(
                            ph['score'] + ph['train'], 1e-9), **ph)
+        clip = ''
+        if self.engine.opt.clip_on:
+            # the last step's norm (before clipping); read here only -- it is a host sync
+            gn = self.engine.opt.last_grad_norm()
+            clip = ', grad_norm: {:.6g}'.format(gn)
         print('step:{}, running train loss: {:.6f}, running train acc: {:.2f}%, '
-              'presam_ema_loss: {:.6f}, pool_mean: {:.4f}, {:.3f} ms/step{}'.format(
+              'presam_ema_loss: {:.6f}, pool_mean: {:.4f}{}, {:.3f} ms/step{}'.format(
                   self.step, m['loss_sum'] / cnt, 100 * m['correct'] / cnt, m['ema'],
-                  m['pool_mean'], (time.perf_counter() - t0) * 1e3 / self.cfg.print_every, dev),
+                  m['pool_mean'], clip,
+                  (time.perf_counter() - t0) * 1e3 / self.cfg.print_every, dev),
               flush=True)
         if self.engine.check_order:
             n, first = self.engine.order_violations()
@@ -1691,6 +1703,9 @@ class NativeTrainer(Trainer):
             self.writer.add_scalar('test/acc', test_acc.accuracy, self.step)
             self.writer.add_scalar('train/loss', train_loss.average, self.step)
             self.writer.add_scalar('test/loss', test_loss.average, self.step)
+            if self.engine.opt.clip_on:
+                self.writer.add_scalar('train/grad_norm', self.engine.opt.last_grad_norm(),
+                                       self.step)
         if self.rank == 0:
             print('(Eval) Step: {}, train loss: {}, train acc: {} test loss: {}, test acc: {}'
                   .format(self.step, train_loss, train_acc, test_loss, test_acc), flush=True)

@@ -112,7 +112,7 @@ from .bn import bn_apply, bn_bwd, BnRunTable, sums_numel, sums_total, streaming_
 from .head import head_fwd, head_bwd, mlp_head_fwd, mlp_head_bwd  # noqa: E402
 from .importance import pool_build, is_sample, gather  # noqa: E402
 from .table import ImportanceTable  # noqa: E402
-from .optim import FlatOptimizer, optimizer_spec  # noqa: E402
+from .optim import FlatOptimizer, optimizer_spec, grad_norm, grad_norm_plan, grad_norm_ranges  # noqa: E402
 from .misc import (quantize, pool2d_fwd, maxpool2d_bwd, dwconv_fwd, dwconv_dgrad, dwconv_wgrad, dwconv_wgrad_slab_floats,
                    dwconv_bwd, dwconv_wgrad_reduce_batch, dwconv_wgrad_blocks,  # noqa: E402
                    nchw_to_nhwc8, tern_pack, tern_unpack)
@@ -123,7 +123,7 @@ from .attention import attn_pool_fwd, attn_pool_bwd, AttnPoolFunction, attn_pool
 __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_fwd', 'pwconv_fwd', 'stem_fwd', 'conv_dgrad', 'conv_wgrad', 'conv_bwd', 'pick_tiles',
            'pack_conv_weight', 'to_nhwc', 'from_nhwc', 'bn_apply', 'bn_bwd', 'BnRunTable', 'sums_numel', 'sums_total', 'streaming_stores',
            'head_fwd', 'head_bwd', 'mlp_head_fwd', 'mlp_head_bwd', 'pool_build', 'is_sample', 'gather', 'ImportanceTable',
-           'FlatOptimizer', 'optimizer_spec', 'quantize', 'tern_pack', 'tern_unpack', 'pool2d_fwd', 'maxpool2d_bwd',
+           'FlatOptimizer', 'optimizer_spec', 'grad_norm', 'grad_norm_plan', 'grad_norm_ranges', 'quantize', 'tern_pack', 'tern_unpack', 'pool2d_fwd', 'maxpool2d_bwd',
            'dwconv_fwd', 'dwconv_dgrad', 'dwconv_wgrad', 'dwconv_wgrad_slab_floats',
            'dwconv_bwd', 'dwconv_wgrad_reduce_batch', 'dwconv_wgrad_blocks',
            'nchw_to_nhwc8', 'lstm_step_fwd', 'lstm_step_bwd', 'pack_lstm', 'BiLSTMFunction', 'bilstm',

@@ -68,6 +68,7 @@ class Trainer(object):
         self.flat = None
         self.bucketer = None
         self._setup_flat()
+        self._setup_clip()
         self._fc_in = None
         if self.cfg.score == 'gradnorm':
             fcs = [m for m in net.modules() if isinstance(m, torch.nn.Linear)]
@@ -126,6 +127,40 @@ class Trainer(object):
             self.bucketer.finish()
         else:
             self.bucketer.allreduce_now()
+
+    # ------------------------------------------------------------------ gradient clipping
+    def _setup_clip(self):
+        """``cfg.clip_grad_norm`` > 0: clip the (averaged) flat gradient's global L2 norm before
+        every optimizer step, as ``torch.nn.utils.clip_grad_norm_`` does."""
+        from .ops.optim import GN_WS_FLOATS, check_max_norm
+        self.clip_grad_norm = check_max_norm(self.cfg.clip_grad_norm)
+        self._grad_norm = None          # 0-dim tensor: the last step's norm (before clipping)
+        self._clip_buf = None
+        if self.clip_grad_norm > 0 and self.flat.grad.is_cuda:
+            dev = self.flat.grad.device
+            # [0] max_norm, [1] norm, [2] coefficient; then the norm pass's workspace
+            self._clip_buf = torch.zeros(4 + GN_WS_FLOATS, dtype=torch.float32, device=dev)
+            self._clip_buf[0] = self.clip_grad_norm
+
+    def clip_gradients(self):
+        """Scale ``flat.grad`` by min(1, max_norm / (norm + 1e-6)); no host sync.  On a HIP
+        device the norm is the native pass (``ops.grad_norm``); on the CPU it is torch's own
+        two-level norm (per parameter, then over those), so the result is clip_grad_norm_'s."""
+        if not self.clip_grad_norm > 0:
+            return
+        g = self.flat.grad
+        if g.is_cuda:
+            from . import ops
+            b = self._clip_buf
+            ops.grad_norm(g, b[0:1], b[1:3], b[4:])
+            self._grad_norm = b[1]
+            g.mul_(b[2])
+            return
+        from .ops.optim import GN_EPS
+        norms = [torch.linalg.vector_norm(g[off:off + n]) for off, n in self.flat.offsets]
+        total = torch.linalg.vector_norm(torch.stack(norms))
+        self._grad_norm = total
+        g.mul_(torch.clamp(self.clip_grad_norm / (total + GN_EPS), max=1.0))
 
     # ------------------------------------------------------------------ sampling
     def get_next(self):
@@ -205,6 +240,7 @@ class Trainer(object):
         self.average_gradients()
         self.timer.stop(t)
         t = self.timer.start('opt')
+        self.clip_gradients()
         self.optimizer.step()
         self.timer.stop(t)
         running_loss.update(loss.detach(), self.batch_size)
@@ -271,7 +307,9 @@ class Trainer(object):
             print('step:{}, running train loss: {}, running train acc: {}, presam_ema_loss: {}, '
                   'step time:{:.3f}, {}'.format(
                       self.step, running_loss, running_acc, ema, time.perf_counter() - t0,
-                      ', '.join('{}:{:.3f}ms'.format(k, v) for k, v in ph.items())), flush=True)
+                      ', '.join('{}:{:.3f}ms'.format(k, v) for k, v in ph.items())) + (
+                          '' if self._grad_norm is None else
+                          ', grad_norm: {:.6g}'.format(float(self._grad_norm))), flush=True)
         if cfg.eval_every and self.step % cfg.eval_every == 0 and (
                 self.rank == 0 or cfg.eval_all_ranks):
             train_loss, train_acc, test_loss, test_acc = self.evaluate()
@@ -280,6 +318,8 @@ class Trainer(object):
                 self.writer.add_scalar('test/acc', test_acc.accuracy, self.step)
                 self.writer.add_scalar('train/loss', train_loss.average, self.step)
                 self.writer.add_scalar('test/loss', test_loss.average, self.step)
+                if self._grad_norm is not None:
+                    self.writer.add_scalar('train/grad_norm', float(self._grad_norm), self.step)
             if self.rank == 0:
                 print('(Eval) Step: {}, train loss: {}, train acc: {} test loss: {}, test acc: {}'
                       .format(self.step, train_loss, train_acc, test_loss, test_acc), flush=True)
