@@ -8,6 +8,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -617,6 +618,39 @@ PYBIND11_MODULE(_C, m) {
                       P<float>(params)};
     pool_augment_launch(a, S(st));
     check_launch("pool_augment");
+  });
+  m.def("pool_spec", [](uintptr_t shard, uintptr_t labels, uintptr_t ctrl, uintptr_t pool,
+                        uintptr_t pool_label, uintptr_t pool_index, int Ns, int C, int H, int W,
+                        int Pn, int batch, int augment, int shuffle, uint32_t seed, uintptr_t st,
+                        uintptr_t zero, int nzero, int shift, int fmask_n, int fmask_max,
+                        int tmask_n, int tmask_max, float gain_lo, float gain_hi, float fill,
+                        uintptr_t params, int chunks) {
+    if (Ns < 1 || H < 1 || W < 1 || Pn < 1 || batch < 1)
+      throw std::runtime_error("pool_spec: Ns, H, W, P and batch must be positive");
+    if (C < 1 || C > 8)
+      throw std::runtime_error("pool_spec: C must be 1..8");
+    if ((long long)H * W * Pn >= (1LL << 30))     // (the kernel's pixel counter plus one stride)
+      throw std::runtime_error("pool_spec: H*W*P must stay below 2^30");
+    if (shift < 0 || shift > W - 1)
+      throw std::runtime_error("pool_spec: shift must be 0..W-1");
+    if (fmask_n < 0 || fmask_n > 2 || fmask_max < 0 || fmask_max > H)
+      throw std::runtime_error("pool_spec: fmask is (n, Fmax) with n <= 2 and Fmax <= H");
+    if (tmask_n < 0 || tmask_n > 2 || tmask_max < 0 || tmask_max > W)
+      throw std::runtime_error("pool_spec: tmask is (n, Tmax) with n <= 2 and Tmax <= W");
+    if (!std::isfinite(gain_lo) || !std::isfinite(gain_hi) || gain_hi < gain_lo)
+      throw std::runtime_error("pool_spec: gain is (lo, hi), finite, lo <= hi");
+    if (!std::isfinite(fill))
+      throw std::runtime_error("pool_spec: fill must be finite");
+    if (chunks < 0)
+      throw std::runtime_error("pool_spec: chunks >= 0");
+    PoolSpecArgs a{{P<const uint8_t>(shard), P<const int64_t>(labels), P<const int64_t>(ctrl),
+                    P<bf16>(pool), P<int>(pool_label), P<int>(pool_index), Ns, H, W, Pn, batch,
+                    0, 0, augment, shuffle, seed, {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, 0,
+                    P<float>(zero), nzero},
+                   C, shift, fmask_n, fmask_max, tmask_n, tmask_max, gain_lo, gain_hi, fill,
+                   P<float>(params), chunks};
+    pool_spec_launch(a, S(st));
+    check_launch("pool_spec");
   });
   m.def("is_sample", [](uintptr_t losses, uintptr_t ema, uintptr_t ctrl, uintptr_t idx, uintptr_t w,
                         uintptr_t meters, int Pn, int B, int group, int importance, float alpha,

@@ -5,6 +5,8 @@
 //               RandomHorizontalFlip, ToTensor, Normalize (`cifar10/data_loader.py:83-90`)
 //               -> NHWC bf16 with channels padded to 8.  Replaces 352 PIL-augmented
 //               images per step on the CPU.
+// pool_spec   : the same pool from a planar bf16 shard of float inputs (spectrograms) with
+//               time shift, gain and frequency / time masks (SpecRecipe).
 // is_sample   : the whole `update_samples` tail (`pytorch_collab.py:106-117`) in one
 //               workgroup: 10x EMA replay over the cumulative pool means (device-
 //               resident EMAverage), p = (l + alpha*ema)/sum, inverse-CDF draws with
@@ -221,6 +223,102 @@ __global__ __launch_bounds__(256) void pool_augment_kernel(PoolAugmentArgs a) {
 #pragma unroll
     for (int c = 3; c < 8; ++c) o[c] = f2bf(0.f);
     *(bf16x8*)(out + (size_t)px * 8) = o;
+  }
+}
+
+// ---- spectrogram recipes (PoolSpecArgs) ----------------------------------------------------
+// Planar bf16 shard [Ns][C][H][W] (H frequency rows, W frames) -> NHWC8 pool.  Output pixel
+// (f, t): fill inside a frequency or a time band (bands are in OUTPUT coordinates), else fill
+// when ts = t - shift leaves [0, W), else bf16(float(x[c][f][ts]) * gain) -- one fp32 multiply;
+// gain is exactly 1.0f when unset, so values pass through bit for bit.  Channels C..7 are +0.
+//
+// Draws per slot: Philox on the counter (gb, t) of the image kernels, stream words 0x5bec0..2
+// (the image kernels use 0x5eed and 0x5eee):
+//   0x5bec0: .x shift   .y gain      .z width fa   .w start fa
+//   0x5bec1: .x width fb  .y start fb  .z width ta   .w start ta
+//   0x5bec2: .x width tb  .y start tb
+// shift = x % (2 S + 1) - S; width = r % (max + 1), start = r' % (size - width + 1); a mask
+// beyond the recipe's count has width 0 and start 0; augment = 0 draws the identity.
+//
+// Grid (P, chunks): block (slot, k) walks pixels k*256 + tid, stride chunks*256, so a wave's
+// lanes read consecutive frames of one row (2-byte loads) and store 1 KiB contiguously.  Every
+// block of a slot repeats the slot's draws; block (slot, 0) writes labels, index and params.
+__global__ __launch_bounds__(256) void pool_spec_kernel(PoolSpecArgs a) {
+  const PoolBuildArgs& b = a.b;
+  const int slot = blockIdx.x;
+  if (b.zero && blockIdx.y == 0) zero_slice(b);
+  int64_t gb;
+  int t;
+  const uint32_t src = pool_src(b, slot, gb, t);
+  const int H = b.H, W = b.W;
+  int shift = 0;
+  float gain = 1.f;
+  int f0[2] = {0, 0}, fw[2] = {0, 0}, t0[2] = {0, 0}, tw[2] = {0, 0};
+  if (b.augment) {
+    const u32x4 c{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5bec0u};
+    const u32x4 r0 = philox4x32(c, b.seed, 0xA5A5A5A5u);
+    const u32x4 r1 = philox4x32(u32x4{c.x, c.y, c.z, 0x5bec1u}, b.seed, 0xA5A5A5A5u);
+    const u32x4 r2 = philox4x32(u32x4{c.x, c.y, c.z, 0x5bec2u}, b.seed, 0xA5A5A5A5u);
+    shift = (int)(r0.x % (uint32_t)(2 * a.shift + 1)) - a.shift;
+    gain = a.gain_lo + (a.gain_hi - a.gain_lo) * u01(r0.y);
+    const uint32_t wr[4] = {r0.z, r1.x, r1.z, r2.x}, sr[4] = {r0.w, r1.y, r1.w, r2.y};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (k < a.fmask_n) {
+        fw[k] = (int)(wr[k] % (uint32_t)(a.fmask_max + 1));
+        f0[k] = (int)(sr[k] % (uint32_t)(H - fw[k] + 1));
+      }
+      if (k < a.tmask_n) {
+        tw[k] = (int)(wr[2 + k] % (uint32_t)(a.tmask_max + 1));
+        t0[k] = (int)(sr[2 + k] % (uint32_t)(W - tw[k] + 1));
+      }
+    }
+  }
+  if (threadIdx.x == 0 && blockIdx.y == 0) {
+    b.pool_label[slot] = (int)b.labels[src];
+    b.pool_index[slot] = (int)src;
+    if (a.params) {
+      float* p = a.params + (size_t)slot * 12;
+      p[0] = (float)shift;
+      p[1] = gain;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        p[2 + 2 * k] = (float)f0[k];
+        p[3 + 2 * k] = (float)fw[k];
+        p[6 + 2 * k] = (float)t0[k];
+        p[7 + 2 * k] = (float)tw[k];
+      }
+      p[10] = p[11] = 0.f;
+    }
+  }
+  const bf16 fill = f2bf(a.fill), zero = f2bf(0.f);
+  const int npx = H * W;
+  const bf16* img = (const bf16*)b.shard + (size_t)src * a.C * npx;
+  bf16* out = b.pool + (size_t)slot * npx * 8;
+  // (f, tt) follow px without a division per pixel: the stride is qs rows and rs frames
+  const int stride = gridDim.y * 256, qs = stride / W, rs = stride - qs * W;
+  int px = blockIdx.y * 256 + threadIdx.x;
+  int f = px / W, tt = px - f * W;
+  for (; px < npx; px += stride) {
+    const int ts = tt - shift;
+    const bool masked = (f >= f0[0] && f < f0[0] + fw[0]) || (f >= f0[1] && f < f0[1] + fw[1]) ||
+                        (tt >= t0[0] && tt < t0[0] + tw[0]) || (tt >= t0[1] && tt < t0[1] + tw[1]);
+    const bool live = !masked && ts >= 0 && ts < W;
+    const bf16* p = img + (size_t)f * W + (live ? ts : 0);
+    bf16x8 o;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      bf16 v = zero;
+      if (c < a.C) v = live ? f2bf(bf2f(p[(size_t)c * npx]) * gain) : fill;
+      o[c] = v;
+    }
+    *(bf16x8*)(out + (size_t)px * 8) = o;
+    f += qs;
+    tt += rs;
+    if (tt >= W) {
+      tt -= W;
+      ++f;
+    }
   }
 }
 
@@ -476,6 +574,21 @@ void pool_augment_launch(const PoolAugmentArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((pool_augment_kernel<false, true>), g, blk, 0, st, a);
   else
     hipLaunchKernelGGL((pool_augment_kernel<false, false>), g, blk, 0, st, a);
+}
+
+static int pool_spec_chunks(int P, int npx) {
+  // about 2048 blocks (8 per CU) while a block keeps at least four 256-pixel trips to spread
+  // its draws over: measured at 1x101x161, P = 320 is fastest at 4..8 blocks per slot (31.6 us
+  // against 62.8 with one) and P = 32 at 16 (10.1 us against 41.9 with one, 17.6 with 64)
+  const int trips = (npx + 255) / 256;
+  return max(1, min(min((2048 + P - 1) / P, trips / 4), 65535));
+}
+
+void pool_spec_launch(const PoolSpecArgs& a, hipStream_t st) {
+  const int trips = (a.b.H * a.b.W + 255) / 256;
+  const int chunks = a.chunks > 0 ? min(min(a.chunks, trips), 65535)
+                                  : pool_spec_chunks(a.b.P, a.b.H * a.b.W);
+  hipLaunchKernelGGL(pool_spec_kernel, dim3(a.b.P, chunks), dim3(256), 0, st, a);
 }
 
 size_t is_sample_lds(int P, int alias) {

@@ -161,6 +161,22 @@ struct PoolAugmentArgs {
 };
 void pool_augment_launch(const PoolAugmentArgs& a, hipStream_t st);
 
+// Spectrogram recipe (mercury_amd/data/augment.py, SpecRecipe): time shift -> gain -> frequency
+// and time masks in output coordinates, from a PLANAR bf16 shard to the NHWC8 pool.
+struct PoolSpecArgs {
+  PoolBuildArgs b;               // b.shard is bf16 [Ns][C][H][W]; b.H frequency rows, b.W frames
+  int C;                         // stored channels, 1..8 (pool channels C..7 are +0)
+  int shift;                     // time shift drawn from [-shift, shift]
+  int fmask_n, fmask_max;        // frequency masks: how many (0..2), widths drawn from [0, max]
+  int tmask_n, tmask_max;        // time masks likewise
+  float gain_lo, gain_hi;        // gain drawn from [lo, hi) (lo = hi = 1: unset, exactly 1.0f)
+  float fill;                    // value of masked / shifted-in pixels (rounded to bf16 once)
+  float* params;                 // optional [P][12]: shift, gain, f0a, fwa, f0b, fwb, t0a, twa,
+                                 //                   t0b, twb, 0, 0
+  int chunks;                    // blocks per slot (grid.y); 0: the launcher's choice
+};
+void pool_spec_launch(const PoolSpecArgs& a, hipStream_t st);
+
 struct IsSampleArgs {
   const float* losses;           // [P]
   float* ema;                    // [0] value, [1] initialised flag (device-resident EMAverage)

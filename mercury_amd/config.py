@@ -40,6 +40,8 @@ class Config:
     #                                 flip + CIFAR Normalize) | 'dataset' (read from the loaders'
     #                                 dataset.transform) | an AugmentRecipe.parse spec, e.g.
     #                                 'resize=35,crop=32,flip=1,degrees=10,scale=0.9:1.1,norm=none'
+    #                                 | a SpecRecipe.parse spec for float [N][C][F][T] datasets,
+    #                                 e.g. 'spec:shift=8,fmask=2x10,tmask=2x20,gain=0.8:1.2'
     # model / optimisation
     model: str = 'resnet18'
     optimizer: str = 'adam'

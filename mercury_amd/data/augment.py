@@ -23,6 +23,9 @@ GPU tests compare against.  Per output pixel (i, j) of the H x W crop:
 
 Values stay float between the stages.  The CPU transforms round to uint8 after ``Resize``
 and after ``RandomAffine``; the unrounded result is within one uint8 level of theirs.
+
+``SpecRecipe`` (below) is the recipe of float spectrogram inputs: time shift, gain, frequency
+and time masks, run by ``pool_spec_kernel`` from a planar bf16 shard and exact to the bit.
 """
 from __future__ import annotations
 
@@ -273,4 +276,169 @@ class AugmentRecipe:
             y1, y2 = min(max(cut_y - h, 0), H), min(max(cut_y + h, 0), H)
             x1, x2 = min(max(cut_x - h, 0), W), min(max(cut_x + h, 0), W)
             out[y1:y2, x1:x2] = 0
+        return out
+
+
+# ---------------------------------------------------------------------- spectrograms
+SPEC_PARAMS = 12     # shift, gain, f0a, fwa, f0b, fwb, t0a, twa, t0b, twb, 0, 0
+
+
+def _mask(v, name):
+    if len(v) != 2:
+        raise ValueError('SpecRecipe: %s is (n, max)' % name)
+    n, m = int(v[0]), int(v[1])
+    if not 0 <= n <= 2 or m < 0:
+        raise ValueError('SpecRecipe: %s is (n, max) with 0 <= n <= 2 and max >= 0, got %r'
+                         % (name, (n, m)))
+    return n, m
+
+
+@dataclass(frozen=True)
+class SpecRecipe:
+    """Time shift, gain and SpecAugment-style masks for float inputs ``x[c][f][t]`` (``f < H``
+    frequency rows, ``t < W`` frames), run by ``pool_spec_kernel`` (``csrc/importance.hip``) on a
+    planar bf16 shard [Ns][C][H][W] for a whole pool: ``ops.pool_build(..., recipe=r)``.
+
+    Output pixel ``y[f][t][c]`` of the NHWC8 pool, given the slot's draws:
+
+    1. ``fill`` if ``f`` lies in a frequency band ``[f0, f0+fw)`` or ``t`` in a time band
+       ``[t0, t0+tw)`` -- bands are in OUTPUT coordinates, applied after the shift;
+    2. else ``ts = t - shift``; ``fill`` if ``ts < 0`` or ``ts >= W``;
+    3. else ``bf16(float(x[c][f][ts]) * gain)``, one fp32 multiply rounded to nearest even.
+       With ``gain=None`` the factor is exactly 1.0, so values pass through bit for bit.
+
+    Channels ``C..7`` are +0; ``fill`` is rounded to bf16 once.  Draws, per pool slot (Philox on
+    the image kernels' counter ``(gb, t)``, stream words 0x5bec0..0x5bec2 of its own):
+    ``shift = r % (2*shift_max + 1) - shift_max``; each mask ``w = r % (max + 1)``,
+    ``start = r' % (size - w + 1)``, masks beyond ``n`` have width 0;
+    ``gain = lo + (hi - lo) * u01(r)``; with ``augment=False`` every draw is the identity."""
+    shift: int = 0                                  # maximum time shift in frames
+    fmask: Tuple[int, int] = (0, 0)                 # (n, Fmax): frequency masks
+    tmask: Tuple[int, int] = (0, 0)                 # (n, Tmax): time masks
+    gain: Optional[Tuple[float, float]] = None      # (lo, hi) multiplicative gain
+    fill: float = 0.0
+
+    def __post_init__(self):
+        s = object.__setattr__
+        s(self, 'shift', int(self.shift))
+        s(self, 'fmask', _mask(self.fmask, 'fmask'))
+        s(self, 'tmask', _mask(self.tmask, 'tmask'))
+        s(self, 'fill', float(self.fill))
+        if self.shift < 0:
+            raise ValueError('SpecRecipe: shift is >= 0, got %d' % self.shift)
+        if self.gain is not None:
+            if len(self.gain) != 2:
+                raise ValueError('SpecRecipe: gain is (lo, hi)')
+            s(self, 'gain', (float(self.gain[0]), float(self.gain[1])))
+            if not all(math.isfinite(g) for g in self.gain) or self.gain[0] > self.gain[1]:
+                raise ValueError('SpecRecipe: gain is (lo, hi), finite, lo <= hi, got %r'
+                                 % (self.gain,))
+        if not math.isfinite(self.fill):
+            raise ValueError('SpecRecipe: fill is finite, got %r' % self.fill)
+
+    @classmethod
+    def parse(cls, spec):
+        """``spec:shift=8,fmask=2x10,tmask=2x20,gain=0.8:1.2,fill=0`` (the ``spec:`` prefix is
+        optional here; ``Config.augment`` needs it to tell the two recipe kinds apart)."""
+        spec = spec.strip()
+        if spec.startswith('spec:'):
+            spec = spec[5:]
+        kw = {}
+        for item in (spec.split(',') if spec else []):
+            if '=' not in item:
+                raise ValueError('SpecRecipe.parse: %r is not name=value' % item)
+            k, v = (s.strip() for s in item.split('=', 1))
+            if k == 'shift':
+                kw[k] = int(v)
+            elif k in ('fmask', 'tmask'):
+                nm = v.split('x')
+                if len(nm) != 2:
+                    raise ValueError('SpecRecipe.parse: %s is NxMAX, got %r' % (k, v))
+                kw[k] = (int(nm[0]), int(nm[1]))
+            elif k == 'gain':
+                if v in ('', 'none'):
+                    kw[k] = None
+                else:
+                    g = v.split(':')
+                    if len(g) != 2:
+                        raise ValueError('SpecRecipe.parse: gain is lo:hi, got %r' % v)
+                    kw[k] = (float(g[0]), float(g[1]))
+            elif k == 'fill':
+                kw[k] = float(v)
+            else:
+                raise ValueError('SpecRecipe.parse: unknown key %r' % k)
+        return cls(**kw)
+
+    def spec(self):
+        """The ``parse`` form of this recipe, with the ``spec:`` prefix."""
+        out = ['shift=%d' % self.shift, 'fmask=%dx%d' % self.fmask, 'tmask=%dx%d' % self.tmask]
+        if self.gain is not None:
+            out.append('gain=%r:%r' % self.gain)
+        out.append('fill=%r' % self.fill)
+        return 'spec:' + ','.join(out)
+
+    @property
+    def identity(self):
+        """Nothing on: every draw is the identity whatever the random words."""
+        return (self.shift == 0 and 0 in self.fmask and 0 in self.tmask and self.gain is None)
+
+    def check(self, C, H, W):
+        """Raise unless the recipe fits a [C][H][W] sample; names the field that does not."""
+        if not 1 <= C <= 8:
+            raise ValueError('SpecRecipe: C must be 1..8, got %d' % C)
+        if H < 1 or W < 1:
+            raise ValueError('SpecRecipe: empty sample %dx%d' % (H, W))
+        if self.shift > W - 1:
+            raise ValueError('SpecRecipe: shift %d exceeds W-1 = %d' % (self.shift, W - 1))
+        if self.fmask[1] > H:
+            raise ValueError('SpecRecipe: fmask width %d exceeds H = %d' % (self.fmask[1], H))
+        if self.tmask[1] > W:
+            raise ValueError('SpecRecipe: tmask width %d exceeds W = %d' % (self.tmask[1], W))
+
+    def draw(self, H, W, generator=None):
+        """One slot's draws from torch's RNG, in the kernel's ranges and ``params`` layout."""
+        def ri(n):
+            return int(torch.randint(0, n, (1,), generator=generator).item())
+        p = [0.0] * SPEC_PARAMS
+        p[0] = float(ri(2 * self.shift + 1) - self.shift)
+        p[1] = 1.0
+        if self.gain is not None:
+            lo, hi = self.gain
+            p[1] = lo + (hi - lo) * float(torch.rand(1, generator=generator).item())
+        for base, (n, mx), size in ((2, self.fmask, H), (6, self.tmask, W)):
+            for k in range(n):
+                w = ri(mx + 1)
+                p[base + 2 * k], p[base + 2 * k + 1] = float(ri(size - w + 1)), float(w)
+        return p
+
+    # ---------------------------------------------------------------- CPU reference
+    def reference(self, x, params, dtype=torch.bfloat16):
+        """The recipe on one [C][H][W] sample with explicit draws ``params`` (``SPEC_PARAMS``
+        values, the kernel's layout) -> [H][W][8] ``dtype``, the pool's layout (class
+        docstring).  ``x`` is rounded to ``dtype`` first, as the shard is."""
+        x = torch.as_tensor(x)
+        if x.dim() != 3:
+            raise ValueError('reference: sample must be [C][H][W]')
+        C, H, W = x.shape
+        self.check(C, H, W)
+        p = [float(v) for v in params]
+        if len(p) != SPEC_PARAMS:
+            raise ValueError('reference: params has %d values' % SPEC_PARAMS)
+        shift = int(p[0])
+        gain = torch.tensor(p[1], dtype=torch.float32)
+        x = x.to(dtype).to(torch.float32)
+        fill = torch.tensor(self.fill, dtype=torch.float32).to(dtype)
+        f = torch.arange(H).view(H, 1)
+        t = torch.arange(W).view(1, W)
+        masked = torch.zeros(H, W, dtype=torch.bool)
+        for k in (2, 4):
+            masked |= (f >= int(p[k])) & (f < int(p[k]) + int(p[k + 1]))
+        for k in (6, 8):
+            masked |= (t >= int(p[k])) & (t < int(p[k]) + int(p[k + 1]))
+        ts = t - shift
+        live = ~masked & (ts >= 0) & (ts < W)
+        v = (x[:, :, ts.clamp(0, W - 1).view(W)] * gain).to(dtype)       # [C][H][W]
+        v = torch.where(live.unsqueeze(0), v, fill)
+        out = torch.zeros(H, W, 8, dtype=dtype)
+        out[:, :, :C] = v.permute(1, 2, 0)
         return out

@@ -15,6 +15,8 @@ Resize, RandomCrop, RandomHorizontalFlip, RandomAffine, Normalize, Cutout.
 recipe (``Config.augment = 'dataset'``), so the native engine applies what the
 dataset's transform says; the kernel keeps values in float between the stages,
 where ``Resize`` and ``RandomAffine`` here round to uint8 (at most one level apart).
+``SpecAugment`` is the float-spectrogram counterpart: it carries a ``SpecRecipe`` that the
+pool build runs from a planar bf16 shard (``pool_spec_kernel``).
 """
 from __future__ import annotations
 
@@ -178,6 +180,33 @@ class Cutout(object):
         x1, x2 = np.clip(x - self.length // 2, 0, w), np.clip(x + self.length // 2, 0, w)
         mask[y1:y2, x1:x2] = 0.
         return img * torch.from_numpy(mask).expand_as(img)
+
+
+class SpecAugment(object):
+    """A ``SpecRecipe`` (``data/augment.py``: time shift, gain, frequency and time masks) on one
+    float [C][F][T] tensor: the draws come from torch's RNG (``generator``, default the global
+    one) in the recipe's ranges, the arithmetic is ``SpecRecipe.reference`` in the input's dtype.
+    The eager ``Trainer`` and ``MyLSTM`` run it as the dataset's transform on any device;
+    ``Config(augment='dataset')`` hands its recipe to the native engine's pool build instead."""
+
+    def __init__(self, recipe, generator=None):
+        from .augment import SpecRecipe
+        self.recipe = SpecRecipe.parse(recipe) if isinstance(recipe, str) else recipe
+        if not isinstance(self.recipe, SpecRecipe):
+            raise ValueError('SpecAugment: expected a SpecRecipe or its spec string, got %r'
+                             % (recipe,))
+        self.generator = generator
+        self.last = None                 # the last call's draws (SpecRecipe's params layout)
+
+    def __call__(self, x):
+        x = torch.as_tensor(x)
+        C, F_, T_ = x.shape
+        self.last = self.recipe.draw(F_, T_, self.generator)
+        y = self.recipe.reference(x, self.last, dtype=x.dtype)
+        return y[:, :, :C].permute(2, 0, 1).contiguous()
+
+    def __repr__(self):
+        return 'SpecAugment(%r)' % self.recipe.spec()
 
 
 def cifar_train_transform():

@@ -33,6 +33,7 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
+from ..data.augment import SPEC_PARAMS, SpecRecipe
 from ..ops import hconv, tune
 from ..ops.conv import cpad8, slab_bytes
 from ..parallel.buckets import default_bucket_bytes
@@ -155,7 +156,10 @@ class NativeEngine(object):
         # plain Normalize for evaluation
         self.augment = self._recipe(augment)
         self.eval_augment = self._recipe(eval_augment)
-        self.aug_params = None           # [P][8] fp32: the last pool's draws (set_shard)
+        if isinstance(self.eval_augment, SpecRecipe):
+            raise ValueError('eval_augment: a SpecRecipe augments training pools only')
+        self.aug_params = None           # [P][8] fp32: the last pool's draws (set_shard);
+        #                                  [P][12] for a SpecRecipe
         self.seed = seed
         self.alpha, self.ema_alpha, self.importance = alpha, ema_alpha, importance
         self.world_size = world_size
@@ -800,6 +804,9 @@ class NativeEngine(object):
         """A recipe whose crop is the network's input size (filled in where it has none)."""
         if recipe is None:
             return None
+        if isinstance(recipe, SpecRecipe):
+            recipe.check(self.lw.in_channels, self.H, self.W)
+            return recipe
         recipe = recipe.with_crop((self.H, self.W))
         if recipe.out_hw != (self.H, self.W):
             raise ValueError('augmentation recipe crops to %s but the engine was built for '
@@ -809,9 +816,19 @@ class NativeEngine(object):
     def _device_inputs(self, images, recipe=None):
         """uint8 HWC images stay uint8 [N][H][W][3] (augmented on the fly) -- with a recipe,
         [N][Hs][Ws][3] of any size its crop fits; float inputs [N][C][H][W] (e.g. spectrograms)
-        are converted ONCE to NHWC bf16 [N][H][W][8]."""
+        are converted ONCE to NHWC bf16 [N][H][W][8] -- or, with a ``SpecRecipe``, kept planar
+        as bf16 [N][C][H][W] (the same rounding, one eighth of the bytes at C = 1)."""
         x = torch.as_tensor(np.ascontiguousarray(images)) if not torch.is_tensor(images) \
             else images
+        if isinstance(recipe, SpecRecipe):
+            C = self.lw.in_channels
+            if x.dtype == torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (C, self.H, self.W):
+                raise ValueError('a SpecRecipe needs a float shard [N][%d][%d][%d], got %s %s'
+                                 % (C, self.H, self.W, x.dtype, tuple(x.shape)))
+            out = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device)
+            for s0 in range(0, x.shape[0], 4096):
+                out[s0:s0 + 4096] = x[s0:s0 + 4096].to(self.device, torch.float32)
+            return out
         if x.dtype == torch.uint8 and recipe is not None:
             if x.dim() != 4 or x.shape[3] != 3:
                 raise ValueError('uint8 shard must be [N][Hs][Ws][3], got %s' % (tuple(x.shape),))
@@ -837,12 +854,13 @@ class NativeEngine(object):
 
     def set_shard(self, images, labels):
         """Keep this rank's training shard resident in HBM: uint8 [Ns][H][W][3] images, or
-        float [Ns][C][H][W] inputs pre-converted to NHWC bf16."""
+        float [Ns][C][H][W] inputs pre-converted to NHWC bf16 (planar bf16 under a SpecRecipe)."""
         x = self._device_inputs(images, self.augment)
         if x.shape[0] < 1:
             raise ValueError('empty shard')
         if self.augment is not None and self.aug_params is None:
-            self.aug_params = torch.zeros(self.P, 8, dtype=torch.float32, device=self.device)
+            n = SPEC_PARAMS if isinstance(self.augment, SpecRecipe) else 8
+            self.aug_params = torch.zeros(self.P, n, dtype=torch.float32, device=self.device)
         # (a shard smaller than one batch -- possible for a Dirichlet non-IID split at large
         # world size -- is cycled: every batch is the shard's epoch permutation, wrapped)
         self.shard = x
@@ -1522,17 +1540,29 @@ def _dataset_arrays(loader):
     return np.asarray(x), np.asarray(y)
 
 
+def _image_hw(x):
+    """uint8 [N][H][W][3] images or float [N][C][H][W] inputs -> (H, W)."""
+    return tuple(x.shape[1:3]) if x.dtype == np.uint8 else tuple(x.shape[2:4])
+
+
 def _config_recipes(cfg, presam_loader, test_loader):
     """``Config.augment`` -> (train recipe, eval recipe): 'cifar' keeps the engine's built-in
     pipeline (None, None); 'dataset' reads the loaders' ``dataset.transform``; anything else
-    is an ``AugmentRecipe.parse`` spec, evaluated with its Resize, crop and Normalize only."""
+    is an ``AugmentRecipe.parse`` spec, evaluated with its Resize, crop and Normalize only.
+    A spec starting with ``spec:`` (``SpecRecipe.parse``), or a ``transforms.SpecAugment`` as
+    the train dataset's transform, gives that spectrogram recipe and no eval recipe."""
     from ..data.augment import AugmentRecipe
+    from ..data.transforms import SpecAugment
     spec = getattr(cfg, 'augment', 'cifar')
     if spec == 'cifar':
         return None, None
+    if spec.startswith('spec:'):
+        return SpecRecipe.parse(spec), None
     if spec == 'dataset':
         tr = [getattr(getattr(ld, 'dataset', None), 'transform', None)
               for ld in (presam_loader, test_loader)]
+        if isinstance(tr[0], SpecAugment):
+            return tr[0].recipe, None
         return AugmentRecipe.from_transform(tr[0]), AugmentRecipe.from_transform(tr[1])
     aug = AugmentRecipe.parse(spec)
     return aug, dataclasses.replace(aug, flip=False, degrees=0.0, scale=None, cutout=0)
@@ -1572,7 +1602,9 @@ class NativeTrainer(Trainer):
         osp = ops.optimizer_spec(optimizer)       # raises on anything the kernel cannot run
         x, y = _dataset_arrays(presam_loader)
         aug, eval_aug = _config_recipes(cfg, presam_loader, test_loader)
-        image_hw = tuple(x.shape[1:3]) if aug is None else aug.with_crop(x.shape[1:3]).out_hw
+        image_hw = _image_hw(x)
+        if aug is not None and not isinstance(aug, SpecRecipe):
+            image_hw = aug.with_crop(image_hw).out_hw
         self.engine = NativeEngine(
             net, self.device, self.batch_size, cfg.presample_batches, image_hw=image_hw,
             augment=aug, eval_augment=eval_aug,

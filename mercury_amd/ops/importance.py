@@ -4,6 +4,7 @@ from __future__ import annotations
 import torch
 
 from . import _chk, lib, ptr, stream_ptr
+from ..data.augment import SPEC_PARAMS, SpecRecipe
 from ..data.transforms import CIFAR_MEAN, CIFAR_STD
 
 
@@ -20,8 +21,19 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
     [P][h][w][8] for its crop (h, w).  A crop-and-flip recipe on a shard of the output size
     runs the kernel above; ``force_augment_kernel`` sends it through the recipe kernel too
     (same bits).  ``params``: an fp32 [P][8] buffer that receives each slot's draws
-    (dy, dx, flip, angle_deg, scale, cut_y, cut_x, 0)."""
+    (dy, dx, flip, angle_deg, scale, cut_y, cut_x, 0).
+
+    A ``data.augment.SpecRecipe`` (time shift, gain, frequency / time masks) takes a PLANAR bf16
+    shard [Ns][C][H][W], C <= 8, and a 4-d pool [P][H][W][8] (``pool_spec_kernel``); ``params``
+    is then fp32 [P][12] (shift, gain, f0a, fwa, f0b, fwb, t0a, twa, t0b, twb, 0, 0).  With
+    ``augment=False``, or ``SpecRecipe()``, the pool has the bits of the plain gather from the
+    same samples' NHWC8 shard."""
     _chk(labels, torch.int64, 'labels')
+    if isinstance(recipe, SpecRecipe):
+        if force_augment_kernel:
+            raise ValueError('force_augment_kernel belongs to an AugmentRecipe')
+        return _pool_spec(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed,
+                          augment, shuffle, zero, recipe, params)
     prebuilt = shard.dtype == torch.bfloat16
     if recipe is not None:
         if prebuilt:
@@ -55,13 +67,42 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
     if not prebuilt:
         _chk(shard, torch.uint8, 'shard')
     elif shard.shape[-1] != 8:
-        raise ValueError('pre-converted shard must be NHWC bf16 with 8 channels')
+        raise ValueError('pre-converted shard must be NHWC bf16 with 8 channels (a planar '
+                         '[Ns][C][H][W] shard needs a SpecRecipe), got %s' % (tuple(shard.shape),))
     Ns, H, W, _ = shard.shape
     _chk(pool, torch.bfloat16, 'pool', P * H * W * 8)
     lib().pool_build(ptr(shard), ptr(labels), ptr(ctrl), ptr(pool), ptr(pool_label),
                      ptr(pool_index), Ns, H, W, P, batch, pad, int(flip), int(augment), int(shuffle),
                      int(seed) & 0xffffffff, list(mean), [1.0 / s for s in std], stream_ptr(),
                      int(prebuilt), ptr(zero), zero.numel() if zero is not None else 0)
+
+
+def _pool_spec(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, augment,
+               shuffle, zero, recipe, params, chunks=0):
+    if shard.dtype == torch.uint8:
+        raise ValueError('shard is uint8: a SpecRecipe needs the planar bf16 shard '
+                         '[Ns][C][H][W] (uint8 image shards take an AugmentRecipe)')
+    _chk(shard, torch.bfloat16, 'shard')
+    if pool.dim() != 4 or pool.shape[3] != 8:
+        raise ValueError('pool must be [P][H][W][8] for a SpecRecipe, got %s'
+                         % (tuple(pool.shape),))
+    H, W = int(pool.shape[1]), int(pool.shape[2])
+    if shard.dim() != 4 or tuple(shard.shape[2:]) != (H, W) or not 1 <= shard.shape[1] <= 8:
+        raise ValueError('shard is %s: a SpecRecipe needs the planar bf16 shard [Ns][C][%d][%d] '
+                         'with C <= 8, not an NHWC8 pre-converted one'
+                         % (tuple(shard.shape), H, W))
+    Ns, C = int(shard.shape[0]), int(shard.shape[1])
+    recipe.check(C, H, W)
+    _chk(pool, torch.bfloat16, 'pool', P * H * W * 8)
+    if params is not None:
+        _chk(params, torch.float32, 'params', P * SPEC_PARAMS)
+    lo, hi = recipe.gain or (1.0, 1.0)
+    lib().pool_spec(ptr(shard), ptr(labels), ptr(ctrl), ptr(pool), ptr(pool_label),
+                    ptr(pool_index), Ns, C, H, W, P, batch, int(augment), int(shuffle),
+                    int(seed) & 0xffffffff, stream_ptr(), ptr(zero),
+                    zero.numel() if zero is not None else 0, recipe.shift, recipe.fmask[0],
+                    recipe.fmask[1], recipe.tmask[0], recipe.tmask[1], lo, hi, recipe.fill,
+                    ptr(params), chunks)
 
 
 def is_sample(losses, ema, ctrl, idx, w, P, B, group, alpha=0.5, ema_alpha=0.9, seed=0,
