@@ -34,13 +34,10 @@ def main():
         pro = dict(stats=stats, gamma=gamma, beta=beta, act='relu', count=32 * H * H,
                    keep=an if keep else None)
         from mercury_amd.ops import conv as cv
-        grp = sp.group_rows or sp.M
+        args = cv._igemm_pro_args(yn, wk, out, sp, plan, slab)
 
         def fused():
-            cv.lib().igemm_pro(cv.ptr(yn), cv.ptr(wk), cv.ptr(out), K, 0, 0, K, grp,
-                               cv.ptr(slab) if plan[2] > 1 else 0, H, H, sp.Cp, sp.P, sp.Q, R, R,
-                               1, R // 2, R * R * sp.Cp // 8, K, sp.M, plan[0], plan[1], plan[2],
-                               cv.stream_ptr(), *cv._pro_args(pro, sp))
+            cv.lib().igemm_pro(*args, cv.stream_ptr(), *cv._pro_args(pro, sp))
         t_f = gtime(fused)
         t_c = gtime(lambda: ops.conv_fwd(an, wk, out, sp, slab=slab, plan=plan))
         t_b = gtime(lambda: ops.bn_apply(yn, stats, gamma, beta, an, N * H * H, C,

@@ -502,7 +502,7 @@ class NativeEngine(object):
             su = m.spec[u.name]
             d['stats'] = m.stats[u.name]
             if count:
-                d['count'] = su.group_rows or su.M
+                d['count'] = su.group
             if ghost:
                 d['group_imgs'] = m.group_imgs
         else:
@@ -530,7 +530,7 @@ class NativeEngine(object):
             kw['res'] = self._block_in(m, s.block - 1, x) if s.res == 'in' else None
         if s.pro in ('pg', 'pw'):
             su = m.spec[u.name]
-            kw.update({s.pro: True}, coef=m.coef, group_rows=su.group_rows or su.M)
+            kw.update({s.pro: True}, coef=m.coef, group_rows=su.group)
         return self._bn_desc(m, u, s.act, **kw)
 
     def _conv_fwd(self, m, name, route, x, pro=None):
@@ -547,7 +547,7 @@ class NativeEngine(object):
             ops.pgemm_fwd(x, w, y, sp, stats=stats, bn=m.plan[name, 'pgemm'], pro=pro)
         elif route == 'dwconv':
             ops.dwconv_fwd(x, self._pview(u.w_seg), y, sp.N, sp.H, sp.W, sp.C, sp.P, sp.Q,
-                           sp.stride, sp.pad, stats=stats, group_rows=sp.group_rows or sp.M,
+                           sp.stride, sp.pad, stats=stats, group_rows=sp.group,
                            pro=pro)
         elif route == 'hconv':
             hconv.hconv_fwd(x, w, y, sp, m.plan[name, 'hconv' if pro is None else 'hconv_bn'],
@@ -580,7 +580,7 @@ class NativeEngine(object):
             kw['res_bn'] = (r.get('stats'), r['gamma'], r['beta'],
                             (r['rmean'], r['rvar']) if 'rmean' in r else None)
         ops.bn_apply(m.buf[s.unit, 'y'], d.get('stats'), d['gamma'], d['beta'], out, sp.M, u.K,
-                     group_rows=sp.group_rows or sp.M, act=s.act, eps=BN_EPS,
+                     group_rows=sp.group, act=s.act, eps=BN_EPS,
                      running=(d['rmean'], d['rvar']) if 'rmean' in d else None,
                      res={'in': x, 'sc': m.buf.get((s.unit2, 'y')), None: None}[s.res], **kw)
 
@@ -897,7 +897,7 @@ class NativeEngine(object):
                 sp_t, sp_s = tm.spec[u.name], sm.spec[u.name]
                 rows.append((u.bn.running_mean, u.bn.running_var, tm.stats[u.name],
                              sm.stats[u.name], u.bn.num_batches_tracked, u.K, 1, n_score,
-                             float(sp_t.M), float(sp_s.group_rows or sp_s.M)))
+                             float(sp_t.M), float(sp_s.group)))
             tables.append(ops.BnRunTable(rows, self.device))
         self.bn_table, self.bn_table_uniform = tables
 

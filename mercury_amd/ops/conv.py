@@ -37,24 +37,33 @@ class ConvSpec:
     pad: int = 0
     group_rows: int = 0   # rows per BN ghost group in the output (0 = whole batch)
 
-    @property
-    def Cp(self):
-        return cpad8(self.C)
-
-    @property
-    def P(self):
-        return (self.H + 2 * self.pad - self.R) // self.stride + 1
-
-    @property
-    def Q(self):
-        return (self.W + 2 * self.pad - self.S) // self.stride + 1
-
-    @property
-    def M(self):
-        return self.N * self.P * self.Q
+    Cp = property(lambda self: cpad8(self.C))
+    P = property(lambda self: (self.H + 2 * self.pad - self.R) // self.stride + 1)
+    Q = property(lambda self: (self.W + 2 * self.pad - self.S) // self.stride + 1)
+    M = property(lambda self: self.N * self.P * self.Q)           # output pixels: the GEMM's rows
+    Mx = property(lambda self: self.N * self.H * self.W)          # input pixels: the dgrad's rows
+    group = property(lambda self: self.group_rows if self.group_rows else self.M)   # rows per group
+    kchunks = property(lambda self: self.R * self.S * self.Cp // 8)   # forward K, 8-channel chunks
 
     def flops(self):
         return 2.0 * self.M * self.K * self.R * self.S * self.C
+
+    # launch geometry, in the field order of the structs in csrc/igemm.h
+    def fwd_geom(self):     # ConvGeom: SH SW SC RP RQ R S stride pad Kc Ncols M
+        return (self.H, self.W, self.Cp, self.P, self.Q, self.R, self.S, self.stride, self.pad,
+                self.kchunks, self.K, self.M)
+
+    def dgrad_geom(self):   # ConvGeom of the transposed GEMM: dy is the source, dx the result
+        return (self.P, self.Q, self.K, self.H, self.W, self.R, self.S, self.stride, self.pad,
+                self.R * self.S * self.K // 8, self.Cp, self.Mx)
+
+    def s2_geom(self):      # the stride-2 class bindings' SH SW SC R S stride pad Ncols | H W N
+        return ((self.P, self.Q, self.K, self.R, self.S, self.stride, self.pad, self.Cp),
+                (self.H, self.W, self.N))
+
+    def wgrad_geom(self):   # WgradGeom: N H W C Pp Q K R S stride pad Creal
+        return (self.N, self.H, self.W, self.Cp, self.P, self.Q, self.K, self.R, self.S,
+                self.stride, self.pad, self.C)
 
 
 def pick_tiles(M, Ncols, kchunks, group_rows=0, min_blocks=CU):
@@ -92,8 +101,7 @@ def slab_bytes(M, Ncols, bm, bn, splits):
 
 
 def fwd_plan(spec: ConvSpec, min_blocks=CU):
-    kchunks = spec.R * spec.S * spec.Cp // 8
-    return pick_tiles(spec.M, spec.K, kchunks, spec.group_rows, min_blocks=min_blocks)
+    return pick_tiles(spec.M, spec.K, spec.kchunks, spec.group_rows, min_blocks=min_blocks)
 
 
 def dgrad_plan(spec: ConvSpec):
@@ -101,7 +109,7 @@ def dgrad_plan(spec: ConvSpec):
     half of the pair launch is fastest with narrow 64x64 tiles reaching ~2 blocks per CU
     before any K split (e.g. 32x32x64 3x3: 22 us vs 31 us with 128x64 tiles)."""
     kchunks = spec.R * spec.S * cpad8(spec.K) // 8
-    M, N = spec.N * spec.H * spec.W, spec.Cp
+    M, N = spec.Mx, spec.Cp
     ktiles = math.ceil(kchunks / 8)
     tiles = math.ceil(M / 64) * math.ceil(N / 64)
     if tiles <= 2 * CU and ktiles >= 4:
@@ -207,7 +215,7 @@ def wgrad_plan(spec: ConvSpec):
 
 
 def _slab(slab, need, device):
-    if slab is not None and slab.numel() * slab.element_size() >= need:
+    if need == 0 or (slab is not None and slab.numel() * slab.element_size() >= need):
         return slab
     if slab is None and not torch.cuda.is_current_stream_capturing():
         return torch.zeros((need + 3) // 4, dtype=torch.float32, device=device)
@@ -247,15 +255,49 @@ def _pro_args(pro, spec):
     (optional activation output, [N*H*W][C])."""
     for k in ('stats', 'rmean', 'rvar', 'gamma', 'beta'):
         _chk(pro.get(k), torch.float32, 'pro.' + k)
-    _chk(pro.get('keep'), torch.bfloat16, 'pro.keep', spec.N * spec.H * spec.W * spec.Cp)
-    _chk(pro.get('res'), torch.bfloat16, 'pro.res', spec.N * spec.H * spec.W * spec.Cp)
+    _chk(pro.get('keep'), torch.bfloat16, 'pro.keep', spec.Mx * spec.Cp)
+    _chk(pro.get('res'), torch.bfloat16, 'pro.res', spec.Mx * spec.Cp)
     if pro.get('stats') is None and pro.get('rmean') is None:
         raise ValueError('pro needs stats or running statistics')
-    grp = spec.group_rows if spec.group_rows else spec.M
     return (ptr(pro.get('stats')), ptr(pro.get('rmean')), ptr(pro.get('rvar')), ptr(pro['gamma']),
-            ptr(pro['beta']), ptr(pro.get('keep')), grp, 1.0 / float(pro.get('count', 1)),
+            ptr(pro['beta']), ptr(pro.get('keep')), spec.group, 1.0 / float(pro.get('count', 1)),
             float(pro.get('eps', 1e-5)), _ACT[pro.get('act')], (spec.R // 2) * spec.S + spec.S // 2,
             ptr(pro.get('res')))
+
+
+def _chk_conv(spec, x=None, w=None, out=None, dy=None, wt=None, dx=None, dw=None, stats=None):
+    """dtype and minimum size of each conv operand given, by role (gradients first)."""
+    rs = spec.R * spec.S
+    _chk(dy, torch.bfloat16, 'dy', spec.M * spec.K)
+    _chk(wt, torch.bfloat16, 'wt', spec.Cp * rs * spec.K)
+    _chk(dx, torch.bfloat16, 'dx', spec.Mx * spec.Cp)
+    _chk(x, torch.bfloat16, 'x', spec.Mx * spec.Cp)
+    _chk(w, torch.bfloat16, 'w', spec.K * rs * spec.Cp)
+    _chk(out, torch.bfloat16, 'out', spec.M * spec.K)
+    _chk(dw, torch.float32, 'dw', spec.K * rs * spec.C)
+    _chk(stats, torch.float32, 'stats')
+
+
+# One builder per binding: the arguments of its lambda in csrc/bindings.cpp, in order, up to the
+# stream (tests/test_conv_args.py names every position); where the stream comes mid-list, what
+# follows it is _bw_args' / _pro_args' / _pg_pro_args' tuple.  No validation, no allocation.
+def _igemm_args(src, wt, out, spec: ConvSpec, plan, slab=None, bias=None, stats=None,
+                accumulate=False, trans=False):
+    """``trans``: the dgrad of ``spec`` (src = dy, wt = [C][R][S][K], out = dx)."""
+    epi = (spec.Cp, 0, 0, spec.Cp, spec.Mx) if trans else \
+        (spec.K, ptr(bias), ptr(stats), spec.K, spec.group)
+    return (ptr(src), ptr(wt), ptr(out), *epi, int(accumulate), ptr(slab) if plan[2] > 1 else 0,
+            *(spec.dgrad_geom() if trans else spec.fwd_geom()), *plan[:3], bool(trans))
+
+
+def _igemm_pro_args(x, w, out, spec: ConvSpec, plan, slab=None, bias=None, stats=None):
+    return (ptr(x), ptr(w), ptr(out), spec.K, ptr(bias), ptr(stats), spec.K, spec.group,
+            ptr(slab) if plan[2] > 1 else 0, *spec.fwd_geom(), *plan[:3])
+
+
+def _dual_args(x, w, out, spec: ConvSpec, stats, slab, plan):
+    return [ptr(x), ptr(w), ptr(out), spec.K, ptr(stats), spec.K, spec.group,
+            ptr(slab) if plan[2] > 1 else 0, *spec.fwd_geom(), plan[2]]
 
 
 def conv_fwd(x, w, out, spec: ConvSpec, stats=None, bias=None, slab=None, plan=None,
@@ -263,44 +305,18 @@ def conv_fwd(x, w, out, spec: ConvSpec, stats=None, bias=None, slab=None, plan=N
     """out[M][K] = conv(x NHWC, w [K][R][S][Cp]); optional BN-sum epilogue.  ``pro``: x is the
     producer's raw conv output and its BN + activation are applied while loading (see
     ``pro_ok`` / ``_pro_args``)."""
-    Cp = spec.Cp
-    _chk(x, torch.bfloat16, 'x', spec.N * spec.H * spec.W * Cp)
-    _chk(w, torch.bfloat16, 'w', spec.K * spec.R * spec.S * Cp)
-    _chk(out, torch.bfloat16, 'out', spec.M * spec.K)
-    _chk(stats, torch.float32, 'stats')
-    plan = plan or fwd_plan(spec)
-    bm, bn, splits = plan[:3]
-    if splits > 1:
-        slab = _slab(slab, slab_bytes(spec.M, spec.K, bm, bn, splits), x.device)
-    grp = spec.group_rows if spec.group_rows else spec.M
+    _chk_conv(spec, x=x, w=w, out=out, stats=stats)
+    plan = tuple((plan or fwd_plan(spec))[:3])
+    slab = _slab(slab, slab_bytes(spec.M, spec.K, *plan), x.device)
     if pro is not None:
-        if accumulate or not pro_ok(spec, (bm, bn, splits), keep=pro.get('keep') is not None):
+        if accumulate or not pro_ok(spec, plan, keep=pro.get('keep') is not None):
             raise ValueError('BN-apply prologue not supported for this conv/plan')
-        lib().igemm_pro(ptr(x), ptr(w), ptr(out), spec.K, ptr(bias), ptr(stats), spec.K, grp,
-                        ptr(slab) if splits > 1 else 0, spec.H, spec.W, Cp, spec.P, spec.Q,
-                        spec.R, spec.S, spec.stride, spec.pad, spec.R * spec.S * Cp // 8, spec.K,
-                        spec.M, bm, bn, splits, stream_ptr(), *_pro_args(pro, spec))
+        args = _igemm_pro_args(x, w, out, spec, plan, slab, bias, stats)
+        lib().igemm_pro(*args, stream_ptr(), *_pro_args(pro, spec))
         return out
-    lib().igemm(ptr(x), ptr(w), ptr(out), spec.K, ptr(bias), ptr(stats), spec.K, grp,
-                int(accumulate), ptr(slab) if splits > 1 else 0,
-                spec.H, spec.W, Cp, spec.P, spec.Q, spec.R, spec.S, spec.stride, spec.pad,
-                spec.R * spec.S * Cp // 8, spec.K, spec.M, bm, bn, splits, False, stream_ptr(),
-                *_NO_BW)
+    args = _igemm_args(x, w, out, spec, plan, slab, bias, stats, accumulate)
+    lib().igemm(*args, stream_ptr(), *_NO_BW)
     return out
-
-
-def _dual_args(x, w, out, spec: ConvSpec, stats, slab, plan):
-    _chk(x, torch.bfloat16, 'x', spec.N * spec.H * spec.W * spec.Cp)
-    _chk(w, torch.bfloat16, 'w', spec.K * spec.R * spec.S * spec.Cp)
-    _chk(out, torch.bfloat16, 'out', spec.M * spec.K)
-    _chk(stats, torch.float32, 'stats')
-    bm, bn, splits = plan[:3]
-    if splits > 1:
-        slab = _slab(slab, slab_bytes(spec.M, spec.K, bm, bn, splits), x.device)
-    grp = spec.group_rows if spec.group_rows else spec.M
-    return [ptr(x), ptr(w), ptr(out), spec.K, ptr(stats), spec.K, grp,
-            ptr(slab) if splits > 1 else 0, spec.H, spec.W, spec.Cp, spec.P, spec.Q, spec.R,
-            spec.S, spec.stride, spec.pad, spec.R * spec.S * spec.Cp // 8, spec.K, spec.M, splits]
 
 
 def conv_fwd_dual(a, b):
@@ -313,9 +329,13 @@ def conv_fwd_dual(a, b):
         return False
     if pa[2] > 1 and pb[2] > 1 and a.get('slab') is b.get('slab'):
         return False
-    va = _dual_args(a['x'], a['w'], a['out'], a['spec'], a.get('stats'), a.get('slab'), pa)
-    vb = _dual_args(b['x'], b['w'], b['out'], b['spec'], b.get('stats'), b.get('slab'), pb)
-    return bool(lib().igemm_dual(va, vb, pa[0], pa[1], stream_ptr()))
+    halves = []
+    for d, p in ((a, pa), (b, pb)):
+        sp = d['spec']
+        _chk_conv(sp, x=d['x'], w=d['w'], out=d['out'], stats=d.get('stats'))
+        slab = _slab(d.get('slab'), slab_bytes(sp.M, sp.K, *p[:3]), d['x'].device)
+        halves.append(_dual_args(d['x'], d['w'], d['out'], sp, d.get('stats'), slab, p))
+    return bool(lib().igemm_dual(*halves, pa[0], pa[1], stream_ptr()))
 
 
 PGEMM_BM = 256
@@ -376,7 +396,7 @@ def _pg_pro_args(pro, spec, x):
     (fp32 workspace >= G*2*C)."""
     for k in ('stats', 'rmean', 'rvar', 'gamma', 'beta', 'coef'):
         _chk(pro.get(k), torch.float32, 'pro.' + k)
-    rows = spec.N * spec.H * spec.W
+    rows = spec.Mx
     _chk(pro.get('keep'), torch.bfloat16, 'pro.keep', rows * spec.Cp)
     _chk(pro.get('res'), torch.bfloat16, 'pro.res', rows * spec.Cp)
     if pro.get('stats') is None and pro.get('rmean') is None:
@@ -394,6 +414,13 @@ def _pg_pro_args(pro, spec, x):
             pro['coef'].numel() * 4)
 
 
+def _pgemm_args(x, w, out, stats, spec: ConvSpec, stride, bn, grid):
+    """PgemmArgs (csrc/igemm.h) of a 1x1 conv, the tile width and the grid."""
+    return (ptr(x), ptr(w), ptr(out), ptr(stats), spec.M, spec.K, spec.Cp, spec.K, spec.K,
+            spec.group, x.numel() * 2, w.numel() * 2, out.numel() * 2, spec.H, spec.W, spec.P,
+            spec.Q, stride, bn, int(grid))
+
+
 def pgemm_fwd(x, w, out, spec: ConvSpec, stats=None, bn=None, grid=0, pro=None):
     """out[M][K] = conv1x1(x NHWC, w [K][Cp]) on the persistent LDS-DMA GEMM (+ BN sums).
     ``pro``: x is the producer's raw output; its BN + activation (+ identity residual) is
@@ -402,19 +429,12 @@ def pgemm_fwd(x, w, out, spec: ConvSpec, stats=None, bn=None, grid=0, pro=None):
         raise ValueError('pgemm: 1x1 pad-0 stride-1/2 convs only')
     if pro is not None and spec.stride != 1:
         raise ValueError('pgemm: the input prologue needs a stride-1 conv')
-    Cp = spec.Cp
-    _chk(x, torch.bfloat16, 'x', spec.N * spec.H * spec.W * Cp)
-    _chk(w, torch.bfloat16, 'w', spec.K * Cp)
-    _chk(out, torch.bfloat16, 'out', spec.M * spec.K)
-    _chk(stats, torch.float32, 'stats')
-    grp = spec.group_rows if spec.group_rows else spec.M
+    _chk_conv(spec, x=x, w=w, out=out, stats=stats)
     bn = bn or pgemm_plan(spec)
     if pro is not None and bn == 256:
         bn = 128      # the 256-wide tile has no register room for the prologue
     pa = _PG_NO_PRO if pro is None else _pg_pro_args(pro, spec, x)
-    ok = lib().pgemm(ptr(x), ptr(w), ptr(out), ptr(stats), spec.M, spec.K, Cp, spec.K, spec.K,
-                     grp, x.numel() * 2, w.numel() * 2, out.numel() * 2, spec.H, spec.W, spec.P,
-                     spec.Q, spec.stride, bn, int(grid), stream_ptr(), *pa)
+    ok = lib().pgemm(*_pgemm_args(x, w, out, stats, spec, spec.stride, bn, grid), stream_ptr(), *pa)
     if not ok:
         raise ValueError('pgemm: unsupported shape/tile %s bn=%s' % (spec, bn))
     return out
@@ -457,16 +477,9 @@ def pwconv_fwd(x, w, out, spec: ConvSpec, stats=None, pro=None):
         raise ValueError('pwconv: unsupported conv %s' % (spec,))
     if pro is not None and pro.get('res') is not None:
         raise ValueError('pwconv: no residual prologue')
-    Cp = spec.Cp
-    _chk(x, torch.bfloat16, 'x', spec.N * spec.H * spec.W * Cp)
-    _chk(w, torch.bfloat16, 'w', spec.K * Cp)
-    _chk(out, torch.bfloat16, 'out', spec.M * spec.K)
-    _chk(stats, torch.float32, 'stats')
-    grp = spec.group_rows if spec.group_rows else spec.M
+    _chk_conv(spec, x=x, w=w, out=out, stats=stats)
     pa = _PG_NO_PRO if pro is None else _pg_pro_args(pro, spec, x)
-    ok = lib().pgemm(ptr(x), ptr(w), ptr(out), ptr(stats), spec.M, spec.K, Cp, spec.K, spec.K,
-                     grp, x.numel() * 2, w.numel() * 2, out.numel() * 2, spec.H, spec.W, spec.P,
-                     spec.Q, 1, 0, 0, stream_ptr(), *pa)
+    ok = lib().pgemm(*_pgemm_args(x, w, out, stats, spec, 1, 0, 0), stream_ptr(), *pa)   # bn = 0
     if not ok:
         raise ValueError('pwconv: unsupported shape %s' % (spec,))
     return out
@@ -490,7 +503,7 @@ def stem_fwd(x, w, y, spec: ConvSpec, stats=None, bias=None):
     _chk(stats, torch.float32, 'stats')
     _chk(bias, torch.float32, 'bias', spec.K)
     pq = spec.P * spec.Q
-    grp = spec.group_rows or spec.M
+    grp = spec.group
     if grp % pq:
         raise ValueError('stem: BN groups must be whole images')
     ok = lib().stem_fwd(ptr(x), ptr(w), ptr(bias), ptr(y), ptr(stats), spec.N, spec.H, spec.W,
@@ -535,8 +548,7 @@ def dgrad_s2_ok(spec: ConvSpec):
 def dgrad_s2_plan(spec: ConvSpec):
     """Tiles of the class dgrad: the classes hold a quarter of the rows each, so the tile
     choice follows the total row count (one K slice per tile)."""
-    M = spec.N * spec.H * spec.W
-    N = spec.Cp
+    M, N = spec.Mx, spec.Cp
     bn = 128 if N >= 128 else 64
     bm = 128 if math.ceil(M / 128) * math.ceil(N / bn) >= 2 * CU else 64
     return bm, bn, 1
@@ -550,26 +562,43 @@ def conv_dgrad(dy, wt, dx, spec: ConvSpec, slab=None, plan=None, accumulate=Fals
         raise ValueError('dgrad supports stride 1/2')
     if spec.K % 8:
         raise ValueError('dgrad needs K % 8 == 0')
-    Cp = spec.Cp
-    _chk(dy, torch.bfloat16, 'dy', spec.M * spec.K)
-    _chk(wt, torch.bfloat16, 'wt', Cp * spec.R * spec.S * spec.K)
-    _chk(dx, torch.bfloat16, 'dx', spec.N * spec.H * spec.W * Cp)
-    Mx = spec.N * spec.H * spec.W
+    _chk_conv(spec, dy=dy, wt=wt, dx=dx)
     if dgrad_s2_ok(spec):
         bm, bn, _ = plan or dgrad_s2_plan(spec)
-        if lib().dgrad_s2(ptr(dy), ptr(wt), ptr(dx), Cp, int(accumulate), spec.P, spec.Q,
-                          spec.K, spec.R, spec.S, spec.stride, spec.pad, Cp, bm, bn, spec.H,
-                          spec.W, spec.N, stream_ptr(), *_bw_args(bw, Mx, Cp)):
+        args = _dgrad_s2_args(dy, wt, dx, spec, (bm, bn), accumulate)
+        if lib().dgrad_s2(*args, stream_ptr(), *_bw_args(bw, spec.Mx, spec.Cp)):
             return dx
-    bm, bn, splits = plan or dgrad_plan(spec)
-    if splits > 1:
-        slab = _slab(slab, slab_bytes(Mx, Cp, bm, bn, splits), dy.device)
-    lib().igemm(ptr(dy), ptr(wt), ptr(dx), Cp, 0, 0, Cp, Mx, int(accumulate),
-                ptr(slab) if splits > 1 else 0,
-                spec.P, spec.Q, spec.K, spec.H, spec.W, spec.R, spec.S, spec.stride, spec.pad,
-                spec.R * spec.S * spec.K // 8, Cp, Mx, bm, bn, splits, True, stream_ptr(),
-                *_bw_args(bw, Mx, Cp))
+    plan = tuple(plan or dgrad_plan(spec))
+    slab = _slab(slab, slab_bytes(spec.Mx, spec.Cp, *plan), dy.device)
+    args = _igemm_args(dy, wt, dx, spec, plan, slab, accumulate=accumulate, trans=True)
+    lib().igemm(*args, stream_ptr(), *_bw_args(bw, spec.Mx, spec.Cp))
     return dx
+
+
+def _dgrad_s2_args(dy, wt, dx, spec: ConvSpec, tile, accumulate=False):
+    pre, post = spec.s2_geom()
+    return (ptr(dy), ptr(wt), ptr(dx), spec.Cp, int(accumulate), *pre, *tile[:2], *post)
+
+
+def _wgrad_args(dy, x, dw, spec: ConvSpec, plan, wslab=0):
+    return (ptr(dy), ptr(x), ptr(dw), *spec.wgrad_geom(), *plan[:3], wslab)
+
+
+def _pair_args(dy, wt, dx, x, dw, spec: ConvSpec, dplan, wplan, slab=None, accumulate=False,
+               bw=_NO_BW, wslab=0):
+    """Also conv_bwd_pair_sc's first tuple.  ``bw``: _bw_args' tuple; ``wslab``: _wslab_ptr's."""
+    wg = spec.wgrad_geom()
+    return (ptr(dy), ptr(wt), ptr(dx), spec.Cp, int(accumulate),
+            ptr(slab) if dplan[2] > 1 else 0, *spec.dgrad_geom(), *dplan[:3], *bw, ptr(x), ptr(dw),
+            *wg[:7], wg[11], *wplan[:3], wslab)
+
+
+def _pair_s2_args(dy, wt, dx, x, dw, spec: ConvSpec, wplan, accumulate=False, bw=_NO_BW,
+                  wslab=0):
+    """Also conv_bwd_pair_sc's second tuple: the class dgrad at its 64 x 64 tiles."""
+    wg = spec.wgrad_geom()
+    return (*_dgrad_s2_args(dy, wt, dx, spec, (64, 64), accumulate), *bw, ptr(x), ptr(dw),
+            *wg[3:7], wg[11], *wplan[:3], wslab)
 
 
 def wgrad_slab_bytes(spec: ConvSpec, plan):
@@ -591,22 +620,19 @@ def conv_wgrad(dy, x, dw, spec: ConvSpec, plan=None, slab=None):
     """dw[K][R][S][C] (fp32, channel padding dropped) += / = wgrad(dy, x).  With ``slab``
     (>= wgrad_slab_bytes, zero-initialised once) the pixel splits reduce through it and dw is
     stored; without, split plans add into dw atomically (dw must start at zero)."""
-    _chk(dy, torch.bfloat16, 'dy', spec.M * spec.K)
-    _chk(x, torch.bfloat16, 'x', spec.N * spec.H * spec.W * spec.Cp)
-    _chk(dw, torch.float32, 'dw', spec.K * spec.R * spec.S * spec.C)
+    _chk_conv(spec, dy=dy, x=x, dw=dw)
     if spec.K % 8:
         raise ValueError('wgrad needs K % 8 == 0')
     _wg_range(spec)
-    bm, bn, splits = (plan or wgrad_plan(spec))[:3]
-    lib().wgrad(ptr(dy), ptr(x), ptr(dw), spec.N, spec.H, spec.W, spec.Cp, spec.P, spec.Q,
-                spec.K, spec.R, spec.S, spec.stride, spec.pad, spec.C, bm, bn, splits,
-                _wslab_ptr(spec, (bm, bn, splits), slab), stream_ptr())
+    plan = tuple((plan or wgrad_plan(spec))[:3])
+    args = _wgrad_args(dy, x, dw, spec, plan, _wslab_ptr(spec, plan, slab))
+    lib().wgrad(*args, stream_ptr())
     return dw
 
 
 def _wg_range(spec):
     # the wgrad kernel addresses dy and x through buffer resources with 32-bit byte offsets
-    if max(spec.M * spec.K, spec.N * spec.H * spec.W * spec.Cp) * 2 >= 2 ** 31:
+    if max(spec.M * spec.K, spec.Mx * spec.Cp) * 2 >= 2 ** 31:
         raise ValueError('wgrad: an operand exceeds 2 GiB (32-bit buffer offsets)')
 
 
@@ -626,40 +652,27 @@ def conv_bwd(dy, wt, dx, x, dw, spec: ConvSpec, dplan=None, wplan=None, slab=Non
     dx (= conv_dgrad, optional fused BN-backward reduce ``bw``) and dw (= conv_wgrad)."""
     if spec.stride not in (1, 2) or spec.K % 8:
         raise ValueError('conv_bwd needs stride 1/2 and K % 8 == 0')
-    Cp = spec.Cp
-    _chk(dy, torch.bfloat16, 'dy', spec.M * spec.K)
-    _chk(wt, torch.bfloat16, 'wt', Cp * spec.R * spec.S * spec.K)
-    _chk(dx, torch.bfloat16, 'dx', spec.N * spec.H * spec.W * Cp)
-    _chk(x, torch.bfloat16, 'x', spec.N * spec.H * spec.W * Cp)
-    _chk(dw, torch.float32, 'dw', spec.K * spec.R * spec.S * spec.C)
+    _chk_conv(spec, dy=dy, wt=wt, dx=dx, x=x, dw=dw)
     _wg_range(spec)
-    bm, bn, splits = dplan or dgrad_plan(spec)
-    wbm, wbn, wsplits = (wplan or wgrad_plan(spec))[:3]
-    Mx = spec.N * spec.H * spec.W
+    dplan = tuple(dplan or dgrad_plan(spec))
+    wplan = tuple((wplan or wgrad_plan(spec))[:3])
     if dgrad_s2_ok(spec):
         # stride 2: the dgrad as parity classes; at the small train batch in the same launch as
         # the wgrad (64 x 64 class tiles), else two launches with the class dgrad's own tiles
-        if spec.N <= 32 and lib().conv_bwd_pair_s2(
-                ptr(dy), ptr(wt), ptr(dx), Cp, int(accumulate), spec.P, spec.Q, spec.K, spec.R,
-                spec.S, spec.stride, spec.pad, Cp, 64, 64, spec.H, spec.W, spec.N,
-                *_bw_args(bw, Mx, Cp), ptr(x), ptr(dw), Cp, spec.P, spec.Q, spec.K, spec.C, wbm,
-                wbn, wsplits, _wslab_ptr(spec, (wbm, wbn, wsplits), wslab), stream_ptr()):
-            return dx, dw
-        conv_wgrad(dy, x, dw, spec, plan=(wbm, wbn, wsplits), slab=wslab)
+        if spec.N <= 32:
+            args = _pair_s2_args(dy, wt, dx, x, dw, spec, wplan, accumulate,
+                                 _bw_args(bw, spec.Mx, spec.Cp), _wslab_ptr(spec, wplan, wslab))
+            if lib().conv_bwd_pair_s2(*args, stream_ptr()):
+                return dx, dw
+        conv_wgrad(dy, x, dw, spec, plan=wplan, slab=wslab)
         conv_dgrad(dy, wt, dx, spec, plan=dgrad_s2_plan(spec), accumulate=accumulate, bw=bw)
         return dx, dw
-    if splits > 1:
-        slab = _slab(slab, slab_bytes(Mx, Cp, bm, bn, splits), dy.device)
-    ok = lib().conv_bwd_pair(
-        ptr(dy), ptr(wt), ptr(dx), Cp, int(accumulate), ptr(slab) if splits > 1 else 0,
-        spec.P, spec.Q, spec.K, spec.H, spec.W, spec.R, spec.S, spec.stride, spec.pad,
-        spec.R * spec.S * spec.K // 8, Cp, Mx, bm, bn, splits, *_bw_args(bw, Mx, Cp),
-        ptr(x), ptr(dw), spec.N, spec.H, spec.W, Cp, spec.P, spec.Q, spec.K, spec.C, wbm, wbn,
-        wsplits, _wslab_ptr(spec, (wbm, wbn, wsplits), wslab), stream_ptr())
-    if not ok:
-        conv_wgrad(dy, x, dw, spec, plan=(wbm, wbn, wsplits), slab=wslab)
-        conv_dgrad(dy, wt, dx, spec, slab=slab, plan=(bm, bn, splits), accumulate=accumulate,
-                   bw=bw)
+    slab = _slab(slab, slab_bytes(spec.Mx, spec.Cp, *dplan), dy.device)
+    args = _pair_args(dy, wt, dx, x, dw, spec, dplan, wplan, slab, accumulate,
+                      _bw_args(bw, spec.Mx, spec.Cp), _wslab_ptr(spec, wplan, wslab))
+    if not lib().conv_bwd_pair(*args, stream_ptr()):
+        conv_wgrad(dy, x, dw, spec, plan=wplan, slab=wslab)
+        conv_dgrad(dy, wt, dx, spec, slab=slab, plan=dplan, accumulate=accumulate, bw=bw)
     return dx, dw
 
 
@@ -673,32 +686,19 @@ def conv_bwd_sc(a, b):
     sa, sb = a['spec'], b['spec']
     if sa.stride != 1 or sa.K % 8 or not dgrad_s2_ok(sb) or sb.N > 32:
         return False
-    bm, bn, splits = a.get('dplan') or dgrad_plan(sa)
-    wbm, wbn, wsplits = (a.get('wplan') or wgrad_plan(sa))[:3]
-    sbm, sbn, ssplits = (b.get('wplan') or wgrad_plan(sb))[:3]
-    if (sbm, sbn) != (64, 64):
+    dplan = tuple(a.get('dplan') or dgrad_plan(sa))
+    wplan = tuple((a.get('wplan') or wgrad_plan(sa))[:3])
+    splan = tuple((b.get('wplan') or wgrad_plan(sb))[:3])
+    if splan[:2] != (64, 64):
         return False
     for d, sp in ((a, sa), (b, sb)):
-        _chk(d['dy'], torch.bfloat16, 'dy', sp.M * sp.K)
-        _chk(d['wt'], torch.bfloat16, 'wt', sp.Cp * sp.R * sp.S * sp.K)
-        _chk(d['dx'], torch.bfloat16, 'dx', sp.N * sp.H * sp.W * sp.Cp)
-        _chk(d['x'], torch.bfloat16, 'x', sp.N * sp.H * sp.W * sp.Cp)
-        _chk(d['dw'], torch.float32, 'dw', sp.K * sp.R * sp.S * sp.C)
+        _chk_conv(sp, dy=d['dy'], wt=d['wt'], dx=d['dx'], x=d['x'], dw=d['dw'])
         _wg_range(sp)
-    Mx = sa.N * sa.H * sa.W
-    slab = a.get('slab')
-    if splits > 1:
-        slab = _slab(slab, slab_bytes(Mx, sa.Cp, bm, bn, splits), a['dy'].device)
-    ta = (ptr(a['dy']), ptr(a['wt']), ptr(a['dx']), sa.Cp, int(a.get('accumulate', False)),
-          ptr(slab) if splits > 1 else 0, sa.P, sa.Q, sa.K, sa.H, sa.W, sa.R, sa.S, sa.stride,
-          sa.pad, sa.R * sa.S * sa.K // 8, sa.Cp, Mx, bm, bn, splits,
-          *_bw_args(a.get('bw'), Mx, sa.Cp), ptr(a['x']), ptr(a['dw']), sa.N, sa.H, sa.W, sa.Cp,
-          sa.P, sa.Q, sa.K, sa.C, wbm, wbn, wsplits, 0)
-    Mb = sb.N * sb.H * sb.W
-    tb = (ptr(b['dy']), ptr(b['wt']), ptr(b['dx']), sb.Cp, int(b.get('accumulate', False)),
-          sb.P, sb.Q, sb.K, sb.R, sb.S, sb.stride, sb.pad, sb.Cp, 64, 64, sb.H, sb.W, sb.N,
-          *_bw_args(None, Mb, sb.Cp), ptr(b['x']), ptr(b['dw']), sb.Cp, sb.P, sb.Q, sb.K, sb.C,
-          sbm, sbn, ssplits, 0)
+    slab = _slab(a.get('slab'), slab_bytes(sa.Mx, sa.Cp, *dplan), a['dy'].device)
+    ta = _pair_args(a['dy'], a['wt'], a['dx'], a['x'], a['dw'], sa, dplan, wplan, slab,
+                    a.get('accumulate', False), _bw_args(a.get('bw'), sa.Mx, sa.Cp))
+    tb = _pair_s2_args(b['dy'], b['wt'], b['dx'], b['x'], b['dw'], sb, splan,
+                       b.get('accumulate', False))
     return bool(lib().conv_bwd_pair_sc(ta, tb, stream_ptr()))
 
 

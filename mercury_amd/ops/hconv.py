@@ -15,7 +15,7 @@ import math
 import torch
 
 from . import _chk, lib, ptr, stream_ptr
-from .conv import ConvSpec, slab_bytes
+from .conv import _ACT, ConvSpec, slab_bytes
 
 HRMAX_PIX = 512                 # halo pixels per tile (csrc/hconv.hip HRMAX pieces x 32 pixels)
 LDS_MAX = 160 * 1024            # one workgroup may take the whole 160 KiB of a CU
@@ -24,7 +24,6 @@ PSLOT = 6                       # persistent kernel's weight ring (csrc PSLOT)
 PERSIST_TILES = ((256, 64), (128, 64), (64, 64))   # (BN = 128 rings exceed 160 KiB)
 TILES = ((256, 64, 4), (128, 64, 2), (64, 64, 1), (256, 128, 4), (128, 128, 2), (64, 128, 1))
 _WM = {(bm, bn): wm for bm, bn, wm in TILES}
-_ACT = {None: 0, 'none': 0, 'relu': 1, 'relu6': 2}
 
 # ds_read_b128 lane groups (MI355X_MICROARCH.md §LDS): one LDS cycle per group when its 16
 # lanes hit 16 distinct 16-byte bank quads
@@ -133,10 +132,9 @@ def row_ok(spec: ConvSpec, bm, bn, stats=True, bias=None, pro=None):
     halo_rows = (tr if img == 1 else spec.P) + 2
     if halo_rows >= 63 or img * spec.H * spec.W * spec.C * 2 >= (1 << 26):
         return False
-    if spec.N * spec.H * spec.W * spec.C * 2 >= (1 << 31):
+    if spec.Mx * spec.C * 2 >= (1 << 31):
         return False
-    grp = spec.group_rows or spec.M
-    return not stats or grp % bm == 0
+    return not stats or spec.group % bm == 0
 
 
 def persistent_ok(spec: ConvSpec, bm, bn, stats=True, bias=None, pro=None):
@@ -154,8 +152,7 @@ def persistent_ok(spec: ConvSpec, bm, bn, stats=True, bias=None, pro=None):
     vr = ts[0] * ts[1] * spec.Q
     if spec.M % vr or spec.K % bn:
         return False
-    grp = spec.group_rows or spec.M
-    return not stats or grp % vr == 0
+    return not stats or spec.group % vr == 0
 
 
 # padded tiles whose valid rows are below this fraction of BM are not offered
@@ -498,9 +495,15 @@ def _pro_args(pro, spec):
             float(pro.get('eps', 1e-5)), _ACT[pro.get('act')])
 
 
+def _hconv_args(x, w, out, bias, stats, spec: ConvSpec, slab, g, plan_):
+    """hconv's arguments up to the stream (csrc/bindings.cpp); ``g``: the geometry dict."""
+    return (ptr(x), ptr(w), ptr(out), ptr(bias), ptr(stats), spec.group,
+            ptr(slab) if plan_[2] > 1 else 0, [int(g[k]) for k in _ORDER], *plan_[:3])
+
+
 def hconv_fwd(x, w, out, spec: ConvSpec, plan_=None, stats=None, bias=None, slab=None, pro=None):
     """out[M][K] = conv(pro(x) NHWC, w [K][R][S][C]) with the fused BN-statistics epilogue."""
-    _chk(x, torch.bfloat16, 'x', spec.N * spec.H * spec.W * spec.C)
+    _chk(x, torch.bfloat16, 'x', spec.Mx * spec.C)
     _chk(w, torch.bfloat16, 'w', spec.K * spec.R * spec.S * spec.C)
     _chk(out, torch.bfloat16, 'out', spec.M * spec.K)
     _chk(stats, torch.float32, 'stats')
@@ -517,24 +520,18 @@ def hconv_fwd(x, w, out, spec: ConvSpec, plan_=None, stats=None, bias=None, slab
             raise ValueError('hconv: row-step tile %dx%d does not fit this conv' % (bm, bn))
         if not row_ok(spec, bm, bn, stats is not None, bias, pro):
             raise ValueError('hconv: the row-step plan does not take this conv')
-        grp = spec.group_rows if spec.group_rows else spec.M
-        lib().hconv(ptr(x), ptr(w), ptr(out), ptr(bias), ptr(stats), grp, 0,
-                    [int(g[k]) for k in _ORDER], bm, bn, splits, stream_ptr(),
-                    *_pro_args(pro, spec))
-        return out
-    extra = persist_table_bytes(spec, pro) if splits == 0 else 0
-    if g is None or lds_bytes(g, bm, bn, splits) + extra > LDS_MAX:
-        raise ValueError('hconv: tile %dx%d does not fit this conv' % (bm, bn))
-    if splits == 0 and not persistent_ok(spec, bm, bn, stats is not None, bias, pro):
-        raise ValueError('hconv: the persistent plan does not take this conv')
-    if pro is not None and splits != 0:
-        raise ValueError('hconv: only the persistent plans take the input BN in staging')
-    if splits > 1:
-        need = slab_bytes(spec.M, spec.K, bm, bn, splits)
-        if slab is None or slab.numel() * slab.element_size() < need:
-            raise ValueError('hconv: split-K slab too small')
-    grp = spec.group_rows if spec.group_rows else spec.M
-    lib().hconv(ptr(x), ptr(w), ptr(out), ptr(bias), ptr(stats), grp,
-                ptr(slab) if splits > 1 else 0, [int(g[k]) for k in _ORDER], bm, bn, splits,
-                stream_ptr(), *_pro_args(pro, spec))
+    else:
+        extra = persist_table_bytes(spec, pro) if splits == 0 else 0
+        if g is None or lds_bytes(g, bm, bn, splits) + extra > LDS_MAX:
+            raise ValueError('hconv: tile %dx%d does not fit this conv' % (bm, bn))
+        if splits == 0 and not persistent_ok(spec, bm, bn, stats is not None, bias, pro):
+            raise ValueError('hconv: the persistent plan does not take this conv')
+        if pro is not None and splits != 0:
+            raise ValueError('hconv: only the persistent plans take the input BN in staging')
+        if splits > 1:
+            need = slab_bytes(spec.M, spec.K, bm, bn, splits)
+            if slab is None or slab.numel() * slab.element_size() < need:
+                raise ValueError('hconv: split-K slab too small')
+    args = _hconv_args(x, w, out, bias, stats, spec, slab, g, (bm, bn, splits))
+    lib().hconv(*args, stream_ptr(), *_pro_args(pro, spec))
     return out

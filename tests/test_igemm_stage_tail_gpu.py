@@ -138,8 +138,9 @@ def test_tail_forward_split_stage_counts(splits, tile, kind):
 def _pair(ops, case, kind, dplan, wplan, wslab=False):
     """dgrad + wgrad of a stride-1 conv through the pair launcher itself (conv_bwd_pair: no
     fallback to separate launches); skips where it has no instantiation for the tiles"""
-    from mercury_amd.ops.conv import (ConvSpec, _NO_BW, _wslab_ptr, slab_bytes, wgrad_slab_bytes)
-    from mercury_amd.ops import ptr, stream_ptr
+    from mercury_amd.ops.conv import (ConvSpec, _pair_args, _wslab_ptr, slab_bytes,
+                                      wgrad_slab_bytes)
+    from mercury_amd.ops import stream_ptr
     x, w, gy = _data(case, kind)[:3]
     spec = ConvSpec(*case)
     Cp, Mx = spec.Cp, spec.N * spec.H * spec.W
@@ -147,15 +148,11 @@ def _pair(ops, case, kind, dplan, wplan, wslab=False):
     dx = torch.empty(Mx, Cp, dtype=torch.bfloat16, device=DEV)
     dw = torch.zeros(spec.K * spec.R * spec.S * spec.C, device=DEV)
     bm, bn, splits = dplan
-    wbm, wbn, wsplits = wplan
     slab = torch.zeros(max(1, slab_bytes(Mx, Cp, bm, bn, splits) // 4), device=DEV)
     ws = torch.zeros(max(1, wgrad_slab_bytes(spec, wplan) // 4), device=DEV) if wslab else None
-    ok = ops.lib().conv_bwd_pair(
-        ptr(dy), ptr(wt), ptr(dx), Cp, 0, ptr(slab) if splits > 1 else 0,
-        spec.P, spec.Q, spec.K, spec.H, spec.W, spec.R, spec.S, spec.stride, spec.pad,
-        spec.R * spec.S * spec.K // 8, Cp, Mx, bm, bn, splits, *_NO_BW,
-        ptr(xn), ptr(dw), spec.N, spec.H, spec.W, Cp, spec.P, spec.Q, spec.K, spec.C, wbm, wbn,
-        wsplits, _wslab_ptr(spec, wplan, ws), stream_ptr())
+    args = _pair_args(dy, wt, dx, xn, dw, spec, dplan, wplan, slab,
+                      wslab=_wslab_ptr(spec, wplan, ws))
+    ok = ops.lib().conv_bwd_pair(*args, stream_ptr())
     if not ok:
         assert (bm, bn) != (64, 64), 'the 64 x 64 pair must launch'
         pytest.skip('no pair instantiation for tiles %s / %s' % (dplan, wplan))
@@ -206,8 +203,8 @@ def test_tail_pair_wgrad_pixel_stage_counts(case, wsplits, wtile, kind):
 def test_tail_pair_s2_class_stage_counts(case, kind):
     """bwd_pair_s2_kernel: the parity classes of a 3x3 stride-2 dgrad reduce over 1, 2, 2 and 4
     taps -- 1/2/2/4 stages at K = 64, 2/4/4/8 at K = 128; a 1x1's only class over 1 or 2"""
-    from mercury_amd.ops.conv import ConvSpec, _NO_BW
-    from mercury_amd.ops import ptr, stream_ptr
+    from mercury_amd.ops.conv import ConvSpec, _pair_s2_args
+    from mercury_amd.ops import stream_ptr
     ops = _ops()
     x, w, gy = _data(case, kind)[:3]
     spec = ConvSpec(*case)
@@ -215,9 +212,7 @@ def test_tail_pair_s2_class_stage_counts(case, kind):
     dy, wt, xn = ops.to_nhwc(gy), ops.pack_conv_weight(w)[1], ops.to_nhwc(x)
     dx = torch.empty(Mx, Cp, dtype=torch.bfloat16, device=DEV)
     dw = torch.zeros(spec.K * spec.R * spec.S * spec.C, device=DEV)
-    ok = ops.lib().conv_bwd_pair_s2(
-        ptr(dy), ptr(wt), ptr(dx), Cp, 0, spec.P, spec.Q, spec.K, spec.R, spec.S, spec.stride,
-        spec.pad, Cp, 64, 64, spec.H, spec.W, spec.N, *_NO_BW, ptr(xn), ptr(dw), Cp, spec.P,
-        spec.Q, spec.K, spec.C, 64, 64, 1, 0, stream_ptr())
+    args = _pair_s2_args(dy, wt, dx, xn, dw, spec, (64, 64, 1))
+    ok = ops.lib().conv_bwd_pair_s2(*args, stream_ptr())
     assert ok, 'the 64 x 64 stride-2 pair must launch'
     _check_pair(dx, dw, case, kind)

@@ -731,12 +731,8 @@ def conv_pro_direct(ops, x, wk, out, spec, slab, plan, pro):
     """conv_fwd(pro=...) without the engine's pointwise-only policy (the kernel takes any
     R x S; the policy is a speed choice)."""
     from mercury_amd.ops import conv as cv
-    grp = spec.group_rows if spec.group_rows else spec.M
-    cv.lib().igemm_pro(cv.ptr(x), cv.ptr(wk), cv.ptr(out), spec.K, 0, 0, spec.K, grp,
-                       cv.ptr(slab) if plan[2] > 1 else 0, spec.H, spec.W, spec.Cp, spec.P, spec.Q,
-                       spec.R, spec.S, spec.stride, spec.pad, spec.R * spec.S * spec.Cp // 8,
-                       spec.K, spec.M, plan[0], plan[1], plan[2], cv.stream_ptr(),
-                       *cv._pro_args(pro, spec))
+    args = cv._igemm_pro_args(x, wk, out, spec, plan, slab)
+    cv.lib().igemm_pro(*args, cv.stream_ptr(), *cv._pro_args(pro, spec))
 
 
 @pytest.mark.parametrize('mode', ['train_keep', 'ghost', 'eval'])
