@@ -20,65 +20,11 @@
 // loads, which hipcc serialises behind one vmcnt(0) each (a ~15 us prologue).
 #include <stdexcept>
 
-#include "common.h"
+#include "bn_math.h"
 #include "kernels.h"
 
 namespace {
 constexpr int NT = 256;
-
-MA_DEV float act_fwd(float v, int act) {
-  if (act == 1) return fmaxf(v, 0.f);
-  if (act == 2) return fminf(fmaxf(v, 0.f), 6.f);
-  return v;
-}
-// derivative from the activation OUTPUT
-MA_DEV float act_mask(float out, int act) {
-  if (act == 1) return out > 0.f ? 1.f : 0.f;
-  if (act == 2) return (out > 0.f && out < 6.f) ? 1.f : 0.f;
-  return 1.f;
-}
-
-MA_DEV void load8(const float* p, float (&v)[8]) {
-  const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
-// scale/shift for 8 channels: from batch sums (sum, sumsq) or running (mean, var).
-MA_DEV void scale_shift8(const float* mean_or_sum, const float* var_or_sq, bool running,
-                         float inv_cnt, float eps, const float* gamma, const float* beta,
-                         float (&sc)[8], float (&sh)[8]) {
-  float a[8], b[8], g[8], be[8];
-  load8(mean_or_sum, a);
-  load8(var_or_sq, b);
-  load8(gamma, g);
-  load8(beta, be);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    float mean, var;
-    if (running) {
-      mean = a[k];
-      var = b[k];
-    } else {
-      mean = a[k] * inv_cnt;
-      var = fmaxf(b[k] * inv_cnt - mean * mean, 0.f);
-    }
-    sc[k] = g[k] * rsqrtf(var + eps);
-    sh[k] = be[k] - mean * sc[k];
-  }
-}
-
-MA_DEV void mean_rstd8(const float* stats, int ld, float inv_cnt, float eps, float (&mean)[8],
-                       float (&rstd)[8]) {
-  float s[8], ss[8];
-  load8(stats, s);
-  load8(stats + ld, ss);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    mean[k] = s[k] * inv_cnt;
-    rstd[k] = rsqrtf(fmaxf(ss[k] * inv_cnt - mean[k] * mean[k], 0.f) + eps);
-  }
-}
 
 // 16-byte store, streaming (nontemporal) when NTS: the large-batch passes write tensors far
 // larger than L2 + the Infinity Cache that the next kernel re-reads from HBM anyway

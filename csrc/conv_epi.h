@@ -6,7 +6,7 @@
 // reduction by the last-arriving slice.  Included into each kernel TU; everything is in an
 // anonymous namespace.
 #pragma once
-#include "common.h"
+#include "bn_math.h"
 #include "igemm.h"
 
 namespace {
@@ -67,35 +67,8 @@ MA_DEV float row16_sum(float v) {
 }
 
 // ---------------------------------------------------------------- epilogue
-// BN-backward helpers (same arithmetic as bn.hip so fused and standalone reductions agree)
-// act'(out) != 0  <=>  act == none, or lo < out < hi: bounds from the uniform act once, so the
-// per-element test is two compares, one uniform OR and one select -- a runtime act switch inside
-// the unrolled element loop was if-converted into every activation form plus selects.  act ==
-// none passes EVERY value (NaN and +-inf included), exactly like bn.hip's act_mask, so a
-// diverging run is not hidden from the health checks by the fused reduction.
-MA_DEV void bn_act_bounds(int act, float& lo, float& hi) {
-  lo = act == 0 ? -__builtin_huge_valf() : 0.f;
-  hi = act == 2 ? 6.f : __builtin_huge_valf();
-}
-// Forward clamp bounds: act == none clamps against NaN, which v_max/v_min_f32 ignore (they
-// return the non-NaN operand), so the clamp is the identity and a NaN input stays NaN as in
-// bn.hip's act_fwd; relu / relu6 clamp as act_fwd does.
-MA_DEV void act_clamp_bounds(int act, float& lo, float& hi) {
-  lo = act == 0 ? __builtin_nanf("") : 0.f;
-  hi = act == 2 ? 6.f : (act == 0 ? __builtin_nanf("") : __builtin_huge_valf());
-}
-MA_DEV void bn_mean_rstd8(const float* stats, int ld, float inv_cnt, float eps, float (&mean)[8],
-                          float (&rstd)[8]) {
-  const float4 a = *(const float4*)stats, b = *(const float4*)(stats + 4);
-  const float4 c = *(const float4*)(stats + ld), d = *(const float4*)(stats + ld + 4);
-  const float s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  const float ss[8] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    mean[k] = s[k] * inv_cnt;
-    rstd[k] = rsqrtf(fmaxf(ss[k] * inv_cnt - mean[k] * mean[k], 0.f) + eps);
-  }
-}
+// (BN-backward mean / rstd and the activation bounds: bn_math.h, shared with bn.hip so fused and
+// standalone reductions agree)
 
 // Waves are laid out WM x WN (WM * WN = 4): 2 x 2 for the LDS-staged loops, 4 x 1 for the
 // direct-A loop.  acc[tm][tn][j] =
@@ -261,14 +234,14 @@ MA_DEV void epi_rows(EpiPf<BM, BN, EARLY>& pf, const bf16* tile, float* red, con
     for (int k = 0; k < 8; ++k) sdz[k] = sx[k] = sx2[k] = 0.f;
     if constexpr (EARLY) {   // the statistics rows the epilogue staged behind the sums
       const float* sl = red + 8 * BN + ch * 8;
-      bn_mean_rstd8(sl, BN, e.bw_inv_count, e.bw_eps, mean, rstd);
+      mean_rstd8(sl, BN, e.bw_inv_count, e.bw_eps, mean, rstd);
       if constexpr (MODE == 2)
-        bn_mean_rstd8(sl + 2 * BN, BN, e.bw_inv_count, e.bw_eps, mean2, rstd2);
+        mean_rstd8(sl + 2 * BN, BN, e.bw_inv_count, e.bw_eps, mean2, rstd2);
     } else {
       const int colc = n0 + ch * 8, cc = colc < N ? colc : 0;
-      bn_mean_rstd8(e.bw_stats + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean, rstd);
+      mean_rstd8(e.bw_stats + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean, rstd);
       if constexpr (MODE == 2)
-        bn_mean_rstd8(e.bw_stats2 + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean2, rstd2);
+        mean_rstd8(e.bw_stats2 + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean2, rstd2);
     }
   }
 #pragma unroll
@@ -504,8 +477,8 @@ MA_DEV void epilogue(AccT<BM, BN, WM>& acc, char* smem, const EpiParams& e, int 
 #pragma unroll
     for (int k = 0; k < 8; ++k) sdz[k] = sx[k] = sx2[k] = mean2[k] = 0.f, rstd2[k] = 1.f;
     const int cc = colc < N ? colc : 0;
-    bn_mean_rstd8(e.bw_stats + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean, rstd);
-    if (two) bn_mean_rstd8(e.bw_stats2 + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean2, rstd2);
+    mean_rstd8(e.bw_stats + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean, rstd);
+    if (two) mean_rstd8(e.bw_stats2 + cc, e.ldo, e.bw_inv_count, e.bw_eps, mean2, rstd2);
   }
   for (int i = tid; i < BM * CPR; i += NT) {
     const int rl = i / CPR;

@@ -21,7 +21,7 @@
 // chunks of the same pixel, so every wave access is a contiguous run of the NHWC row.
 #include <stdlib.h>
 
-#include "common.h"
+#include "bn_math.h"
 #include "kernels.h"
 
 namespace {
@@ -45,7 +45,7 @@ MA_DEV void load_w72(const float* w, int c8, float (&wr)[9][8]) {
     for (int tap = 0; tap < 9; ++tap) wr[tap][k] = t[k * 9 + tap];
 }
 
-MA_DEV bf16x8 ld8(const bf16* p, bool ok) {
+MA_DEV bf16x8 ld8_or0(const bf16* p, bool ok) {
   bf16x8 v;
   if (ok) {
     v = *(const bf16x8*)p;
@@ -91,8 +91,7 @@ __global__ __launch_bounds__(DT) void dw_fwd_kernel(DwArgs a) {
     load_w72(a.w, c8, wr);
     constexpr int NCOL = (DWL - 1) * S + 3;
     const int q0 = qs * DWL, w0 = q0 * S - a.pad;
-    // input prologue: this thread's 8 channels of its image's statistics group (same arithmetic
-    // as bn.hip); NaN clamp bounds for act none keep NaN (conv_epi.h act_clamp_bounds)
+    // input prologue: this thread's 8 channels of its image's statistics group
     float psc[8], psh[8], plo = 0.f, phi = 0.f;
     if constexpr (PRO) {
       const int ch = c8 * 8;
@@ -101,16 +100,13 @@ __global__ __launch_bounds__(DT) void dw_fwd_kernel(DwArgs a) {
       const float* v0p = a.pro_stats ? m0p + a.C : a.pro_rvar + ch;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        float mean = m0p[k], var = v0p[k];
-        if (a.pro_stats) {
-          mean *= a.pro_inv_count;
-          var = fmaxf(var * a.pro_inv_count - mean * mean, 0.f);
-        }
-        psc[k] = a.pro_gamma[ch + k] * rsqrtf(var + a.pro_eps);
-        psh[k] = a.pro_beta[ch + k] - mean * psc[k];
+        const float m0 = m0p[k], v0 = v0p[k];
+        float mean = m0, var = v0;
+        if (a.pro_stats) bn_mean_var(m0, v0, a.pro_inv_count, mean, var);
+        psc[k] = bn_scale(a.pro_gamma[ch + k], var, a.pro_eps);
+        psh[k] = bn_shift(a.pro_beta[ch + k], mean, psc[k]);
       }
-      plo = a.pro_act == 0 ? __builtin_nanf("") : 0.f;
-      phi = a.pro_act == 2 ? 6.f : (a.pro_act == 0 ? __builtin_nanf("") : __builtin_huge_valf());
+      act_clamp_bounds(a.pro_act, plo, phi);
     }
     float acc[DH][DWL][8];
 #pragma unroll
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(DT) void dw_fwd_kernel(DwArgs a) {
         for (int j = 0; j < NCOL; ++j) {
           const int ww = w0 + j;
           const bool in = ww >= 0 && ww < a.W;
-          col[j] = ld8(row + (size_t)ww * a.C, in);
+          col[j] = ld8_or0(row + (size_t)ww * a.C, in);
           if constexpr (PRO) {
             if (in) {
 #pragma unroll
@@ -211,12 +207,6 @@ __global__ __launch_bounds__(DT) void dw_fwd_kernel(DwArgs a) {
   }
 }
 
-MA_DEV float dw_mask(float out, int act) {       // (bn.hip act_mask)
-  if (act == 1) return out > 0.f ? 1.f : 0.f;
-  if (act == 2) return (out > 0.f && out < 6.f) ? 1.f : 0.f;
-  return 1.f;
-}
-
 // BW: the dgrad also reduces the BN-backward sums of the BN feeding this conv (what
 // bn_bwd_reduce would do in a separate pass over dx, out and y): dz = dx * act'(out),
 // sums += (dz, dz * xhat), block-reduced through padded LDS rows, one atomic pair per channel.
@@ -242,11 +232,9 @@ MA_DEV void dw_dgrad_body(const bf16* dy, const float* w, bf16* dx, int N, int H
     load_w72(w, c8, wr);
     if constexpr (BW) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        mean[k] = bw.stats[c8 * 8 + k] * bw.inv_count;
-        rstd[k] = rsqrtf(fmaxf(bw.stats[C + c8 * 8 + k] * bw.inv_count - mean[k] * mean[k], 0.f) +
-                         bw.eps);
-      }
+      for (int k = 0; k < 8; ++k)
+        bn_mean_rstd(bw.stats[c8 * 8 + k], bw.stats[C + c8 * 8 + k], bw.inv_count, bw.eps, mean[k],
+                     rstd[k]);
     }
   }
   for (int gi = gt; gi < total && gt < lim; gi += stride) {
@@ -262,8 +250,8 @@ MA_DEV void dw_dgrad_body(const bf16* dy, const float* w, bf16* dx, int N, int H
 #pragma unroll
       for (int o = 0; o < DWL; ++o) {
         const bool in = x0 + o < W;
-        ov[o] = ld8(bw.out + rowoff + (size_t)(x0 + o) * C, in);
-        yv[o] = ld8(bw.y + rowoff + (size_t)(x0 + o) * C, in);
+        ov[o] = ld8_or0(bw.out + rowoff + (size_t)(x0 + o) * C, in);
+        yv[o] = ld8_or0(bw.y + rowoff + (size_t)(x0 + o) * C, in);
       }
     }
     float acc[DWL][8];
@@ -282,7 +270,7 @@ MA_DEV void dw_dgrad_body(const bf16* dy, const float* w, bf16* dx, int N, int H
 #pragma unroll
           for (int j = 0; j < DWL + 2; ++j) {
             const int q = x0 + pad - 2 + j;
-            col[j] = ld8(row + (size_t)q * C, q >= 0 && q < Q);
+            col[j] = ld8_or0(row + (size_t)q * C, q >= 0 && q < Q);
           }
 #pragma unroll
           for (int o = 0; o < DWL; ++o)
@@ -319,7 +307,7 @@ MA_DEV void dw_dgrad_body(const bf16* dy, const float* w, bf16* dx, int N, int H
         if constexpr (BW) {
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            const float dz = bf2f(v[k]) * dw_mask(bf2f(ov[o][k]), bw.act);
+            const float dz = bf2f(v[k]) * act_mask(bf2f(ov[o][k]), bw.act);
             sdz[k] += dz;
             sx[k] += dz * (bf2f(yv[o][k]) - mean[k]) * rstd[k];
           }
@@ -406,11 +394,11 @@ MA_DEV void dw_wgrad_body(const bf16* dy, const bf16* x, float* dw, int N, int H
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
         const int ww = q0 * S - pad + t;
-        win[rr][t] = ld8(rows[rr] + (size_t)ww * C, q0 < q1 && rok[rr] && ww >= 0 && ww < W);
+        win[rr][t] = ld8_or0(rows[rr] + (size_t)ww * C, q0 < q1 && rok[rr] && ww >= 0 && ww < W);
       }
     const size_t goff = (size_t)(n * P + p) * Q * C + c8 * 8;
     const bf16* grow = dy + goff;
-    bf16x8 g = ld8(grow + (size_t)q0 * C, q0 < q1);
+    bf16x8 g = ld8_or0(grow + (size_t)q0 * C, q0 < q1);
     for (int q = q0; q < q1; ++q) {
       // column q+1's loads first
       bf16x8 n1[3], n2[3], ng = g;
@@ -418,8 +406,8 @@ MA_DEV void dw_wgrad_body(const bf16* dy, const bf16* x, float* dw, int N, int H
       const bool more = q + 1 < q1;
 #pragma unroll
       for (int rr = 0; rr < 3; ++rr) {
-        if (S == 2) n1[rr] = ld8(rows[rr] + (size_t)(base + 1) * C, more && rok[rr] && base + 1 >= 0 && base + 1 < W);
-        n2[rr] = ld8(rows[rr] + (size_t)(base + 2) * C, more && rok[rr] && base + 2 >= 0 && base + 2 < W);
+        if (S == 2) n1[rr] = ld8_or0(rows[rr] + (size_t)(base + 1) * C, more && rok[rr] && base + 1 >= 0 && base + 1 < W);
+        n2[rr] = ld8_or0(rows[rr] + (size_t)(base + 2) * C, more && rok[rr] && base + 2 >= 0 && base + 2 < W);
       }
       if (more) ng = *(const bf16x8*)(grow + (size_t)(q + 1) * C);
 #pragma unroll

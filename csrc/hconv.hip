@@ -39,11 +39,26 @@ namespace {
 constexpr int NSLOT = 3;     // weight ring slots (prefetch distance 2)
 constexpr int HRMAX = 16;    // halo DMA pieces per wave (32 pixels per piece over 4 waves)
 
-// Activation as one clamp [lo, hi] (none: NaN bounds = identity that keeps NaN, relu: 0..inf,
-// relu6: 0..6; conv_epi.h act_clamp_bounds) -- branch-free: a per-element if-chain on the
-// kernel-uniform selector compiled to two scalar branches per element (255 in one halo
-// transform, ~3x the transform's cost)
-MA_DEV void act_bounds(int act, float& lo, float& hi) { act_clamp_bounds(act, lo, hi); }
+// The halo transforms apply the activation as one clamp [lo, hi] (bn_math.h act_clamp_bounds)
+// -- branch-free: a per-element if-chain on the kernel-uniform selector compiled to two scalar
+// branches per element (255 in one halo transform, ~3x the transform's cost)
+
+// Entry (slot, c) of an LDS table of BN coefficients, [slot][C / 8][scale[8] | shift[8]]: channel
+// c's scale / shift from the sums of statistics group gi, or from the running statistics
+MA_DEV void bn_table_entry(float* tab, const HconvPro& pro, int C, int slot, int gi, int c) {
+  float mean, var;
+  if (pro.stats) {
+    bn_mean_var(pro.stats[(size_t)gi * 2 * C + c], pro.stats[(size_t)gi * 2 * C + C + c],
+                pro.inv_count, mean, var);
+  } else {
+    mean = pro.rmean[c];
+    var = pro.rvar[c];
+  }
+  const float sc = bn_scale(pro.gamma[c], var, pro.eps);
+  float* t = tab + ((size_t)slot * (C >> 3) + (c >> 3)) * 16 + (c & 7);
+  t[0] = sc;
+  t[8] = bn_shift(pro.beta[c], mean, sc);
+}
 
 // 16 bytes per lane, global -> LDS (`global_load_lds_dwordx4`), lane l landing at the wave-uniform
 // LDS address + 16 l.  Issued from inline asm on purpose: the compiler models LDS-DMA as an LDS
@@ -680,7 +695,7 @@ __global__ __launch_bounds__(64 * NW, 1) void hconv_persist_kernel(const bf16* _
   auto xform = [&](int hb_i, int j0, int j1) {
     if constexpr (MODE == 1) {
       float lo, hi;
-      act_bounds(pro.act, lo, hi);
+      act_clamp_bounds(pro.act, lo, hi);
       char* hb = smem + hb_i * HBYTES + (tid >> 3) * 128 + (tid & 7) * 16;
 #pragma unroll
       for (int j = 0; j < HRC; ++j) {
@@ -775,18 +790,7 @@ __global__ __launch_bounds__(64 * NW, 1) void hconv_persist_kernel(const bf16* _
     const int G = pro.stats ? g.N / pro.group_imgs : 1;
     for (int i = tid; i < G * g.C; i += NTP) {
       const int gi = i / g.C, c = i - gi * g.C;
-      float mean, var;
-      if (pro.stats) {
-        mean = pro.stats[(size_t)gi * 2 * g.C + c] * pro.inv_count;
-        var = fmaxf(pro.stats[(size_t)gi * 2 * g.C + g.C + c] * pro.inv_count - mean * mean, 0.f);
-      } else {
-        mean = pro.rmean[c];
-        var = pro.rvar[c];
-      }
-      const float sc = pro.gamma[c] * rsqrtf(var + pro.eps);
-      float* t = coef + ((size_t)gi * (g.C >> 3) + (c >> 3)) * 16 + (c & 7);
-      t[0] = sc;
-      t[8] = pro.beta[c] - mean * sc;
+      bn_table_entry(coef, pro, g.C, gi, gi, c);
     }
   }
   set_halo(m0);
@@ -1085,21 +1089,16 @@ __global__ __launch_bounds__(64 * NW, 1) void hrow_kernel(const bf16* __restrict
       const f32x4 e0 = *(const f32x4*)(pro.beta + ch), e1 = *(const f32x4*)(pro.beta + ch + 4);
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const float a = q < 4 ? a0[q] : a1[q - 4], bb = q < 4 ? b0[q] : b1[q - 4];
-        float mean = a, var = bb;
-        if (pro.stats) {
-          mean = a * pro.inv_count;
-          var = fmaxf(bb * pro.inv_count - mean * mean, 0.f);
-        }
-        csc[q] = (q < 4 ? g0[q] : g1[q - 4]) * rsqrtf(var + pro.eps);
-        csh[q] = (q < 4 ? e0[q] : e1[q - 4]) - mean * csc[q];
+        bn_scale_shift(q < 4 ? a0[q] : a1[q - 4], q < 4 ? b0[q] : b1[q - 4], pro.stats != nullptr,
+                       pro.inv_count, pro.eps, q < 4 ? g0[q] : g1[q - 4],
+                       q < 4 ? e0[q] : e1[q - 4], csc[q], csh[q]);
       }
     }
   };
   auto xform = [&](int hbuf) __attribute__((always_inline)) {
     if constexpr (MODE >= 1) {
       float lo, hi;
-      act_bounds(pro.act, lo, hi);
+      act_clamp_bounds(pro.act, lo, hi);
 #pragma unroll
       for (int i = 0; i < HRC; ++i) {
         if (i > ilast || hoff[i] == OOB) continue;   // (a repeat of piece ilast; padding)
@@ -1207,19 +1206,8 @@ __global__ __launch_bounds__(64 * NW, 1) void hrow_kernel(const bf16* __restrict
       gb = __builtin_amdgcn_readfirstlane(udiv24(mB, PQ, rpq) / pro.group_imgs);
     }
     for (int i = tid; i < 2 * g.C; i += 64 * NW) {
-      const int sl = i >= g.C, c = i - sl * g.C, gi = sl ? gb : ga;
-      float mean, var;
-      if (pro.stats) {
-        mean = pro.stats[(size_t)gi * 2 * g.C + c] * pro.inv_count;
-        var = fmaxf(pro.stats[(size_t)gi * 2 * g.C + g.C + c] * pro.inv_count - mean * mean, 0.f);
-      } else {
-        mean = pro.rmean[c];
-        var = pro.rvar[c];
-      }
-      const float sc = pro.gamma[c] * rsqrtf(var + pro.eps);
-      float* t = ctab + (sl * (g.C >> 3) + (c >> 3)) * 16 + (c & 7);
-      t[0] = sc;
-      t[8] = pro.beta[c] - mean * sc;
+      const int sl = i >= g.C, c = i - sl * g.C;
+      bn_table_entry(ctab, pro, g.C, sl, sl ? gb : ga, c);
     }
   }
   vm_wait<0>();

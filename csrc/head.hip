@@ -12,7 +12,7 @@
 // LDS; dot products are wave64 reductions.
 #include <cstdlib>
 
-#include "common.h"
+#include "bn_math.h"
 #include "kernels.h"
 
 namespace {
@@ -65,16 +65,16 @@ __global__ __launch_bounds__(NT) void head_pool_bn_kernel(HeadArgs a) {
     for (int k = 0; k < 8; ++k) {
       if (a.bn_stats) {
         const float* st = a.bn_stats + (size_t)(b / a.bn_group_imgs) * 2 * a.C + c + k;
-        m8[k] = st[0] * a.bn_inv_count;
-        v8[k] = fmaxf(st[a.C] * a.bn_inv_count - m8[k] * m8[k], 0.f);
+        bn_mean_var(st[0], st[a.C], a.bn_inv_count, m8[k], v8[k]);
       } else {
         m8[k] = a.bn_rmean[c + k];
         v8[k] = a.bn_rvar[c + k];
       }
-      sc[k] = a.bn_gamma[c + k] * rsqrtf(v8[k] + a.bn_eps);
-      sh[k] = a.bn_beta[c + k] - m8[k] * sc[k];
+      sc[k] = bn_scale(a.bn_gamma[c + k], v8[k], a.bn_eps);
+      sh[k] = bn_shift(a.bn_beta[c + k], m8[k], sc[k]);
     }
   }
+  // finite bounds, not act_clamp_bounds: with act none a NaN is clamped away here, not kept
   const float lo = a.bn_act ? 0.f : -3.4e38f, hi = a.bn_act == 2 ? 6.f : 3.4e38f;
   const bf16* x = a.act + (size_t)b * a.HW * a.C + c;
   const bf16* r = a.bn_res ? a.bn_res + (size_t)b * a.HW * a.C + c : nullptr;
@@ -366,10 +366,6 @@ __global__ __launch_bounds__(NT) void head_fwd_kernel(HeadArgs a) {
 // chunks run as separate blocks; the loss / softmax kernel then runs on the ready logits.
 constexpr int HC_CHUNK = 16;
 
-MA_DEV void bn_act_bounds_h(int act, float& lo, float& hi) {   // (conv_epi.h bn_act_bounds)
-  lo = act == 0 ? -__builtin_huge_valf() : 0.f;
-  hi = act == 2 ? 6.f : __builtin_huge_valf();
-}
 __global__ __launch_bounds__(NT) void head_fc_chunk_kernel(HeadArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sh[];
   float* pooled = sh;               // [C]
@@ -437,15 +433,12 @@ __global__ __launch_bounds__(NT) void head_bwd_kernel(HeadBwdArgs a) {
     // the final BN's backward sums over this sample's HW positions of channel c (the reduce
     // pass bn_bwd would otherwise make): same arithmetic as the dgrad epilogue
     float lo, hi;
-    bn_act_bounds_h(a.bw_act, lo, hi);
+    bn_act_bounds(a.bw_act, lo, hi);
     const bool pass = a.bw_act == 0;
-    const float m1 = a.bw_stats[c] * a.bw_inv_count;
-    const float r1 = rsqrtf(fmaxf(a.bw_stats[a.C + c] * a.bw_inv_count - m1 * m1, 0.f) + a.bw_eps);
-    float m2 = 0.f, r2 = 0.f;
-    if (a.bw_y2) {
-      m2 = a.bw_stats2[c] * a.bw_inv_count;
-      r2 = rsqrtf(fmaxf(a.bw_stats2[a.C + c] * a.bw_inv_count - m2 * m2, 0.f) + a.bw_eps);
-    }
+    float m1, r1, m2 = 0.f, r2 = 0.f;
+    bn_mean_rstd(a.bw_stats[c], a.bw_stats[a.C + c], a.bw_inv_count, a.bw_eps, m1, r1);
+    if (a.bw_y2)
+      bn_mean_rstd(a.bw_stats2[c], a.bw_stats2[a.C + c], a.bw_inv_count, a.bw_eps, m2, r2);
     const float g = bf2f(v);
     const size_t base = (size_t)b * a.HW * a.C + c;
     float sdz = 0.f, sx = 0.f, sx2 = 0.f;

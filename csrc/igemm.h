@@ -198,6 +198,9 @@ struct PgemmPro {
   bf16* keep;              // optional activation output [rows][K]
   unsigned res_bytes, keep_bytes, coef_bytes;
 };
+// Fills pro.coef ([G][2][K] scale, shift) from the producer's statistics: one small launch on
+// ``st`` ahead of the pgemm / pwconv kernel that reads it (pgemm.hip).
+void bn_coef_launch(const PgemmPro& pro, int K, hipStream_t st);
 // bn in {64, 128, 256}; grid <= 0: one block per CU.  Returns 0 when unsupported.
 int pgemm_launch(const PgemmArgs& g, int bn, int grid, hipStream_t st, const PgemmPro* pro = nullptr);
 // Narrow-input (K <= 128) stride-1 1x1 conv with the whole A panel (128 rows x K) resident in

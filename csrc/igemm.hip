@@ -373,15 +373,9 @@ MA_DEV void igemm_nt_body(const bf16* __restrict__ src, const bf16* __restrict__
       float plo, phi;
       act_clamp_bounds(pro.act, plo, phi);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {   // same arithmetic as bn.hip scale_shift8
-        float mean = mv[k], var = vv[k];
-        if (pbase) {
-          mean = mv[k] * pro.inv_count;
-          var = fmaxf(vv[k] * pro.inv_count - mean * mean, 0.f);
-        }
-        sc[k] = gv[k] * rsqrtf(var + pro.eps);
-        sh[k] = bv[k] - mean * sc[k];
-      }
+      for (int k = 0; k < 8; ++k)
+        bn_scale_shift(mv[k], vv[k], pbase != nullptr, pro.inv_count, pro.eps, gv[k], bv[k], sc[k],
+                       sh[k]);
       const bool hres = pro.res != nullptr;   // kernel-uniform
 #pragma unroll
       for (int i = 0; i < AR; ++i) {

@@ -2,7 +2,7 @@
 // NCHW fp32 -> NHWC bf16 layout conversion for host-fed tensors.
 #include <stdexcept>
 
-#include "common.h"
+#include "bn_math.h"
 #include "kernels.h"
 
 namespace {
@@ -13,16 +13,6 @@ constexpr int NT = 256;
 // (a 64-bit div/mod is a ~100-instruction call; the ImageNet-stem pool at B=1280 was VALU-bound
 // on it).  The max pool records the window tap r*k+s of each maximum as one byte per channel
 // (first maximum in scan order, like torch), so the backward reads 8 taps as one 8-byte word.
-MA_DEV void ld8(const float* p, float (&v)[8]) {     // 8 floats as two 16-byte loads
-  const float4 x = *(const float4*)p, y = *(const float4*)(p + 4);
-  v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-  v[4] = y.x; v[5] = y.y; v[6] = y.z; v[7] = y.w;
-}
-MA_DEV float pool_act(float v, int act) {
-  if (act == 1) return fmaxf(v, 0.f);
-  if (act == 2) return fminf(fmaxf(v, 0.f), 6.f);
-  return v;
-}
 
 // KS > 0: the window size is a compile-time constant and all KS*KS tap loads are issued
 // before the first is used (out-of-image taps load a clamped in-image pixel and are masked);
@@ -95,20 +85,15 @@ __global__ __launch_bounds__(NT) void pool2d_fwd_kernel(PoolArgs a) {
     const float* s0 = run ? a.rmean + c : a.stats + (size_t)g * 2 * a.C + c;
     const float* s1 = run ? a.rvar + c : s0 + a.C;
     float m8[8], v8[8], g8[8], b8[8];
-    ld8(s0, m8);
-    ld8(s1, v8);
-    ld8(a.gamma + c, g8);
-    ld8(a.beta + c, b8);
+    load8(s0, m8);
+    load8(s1, v8);
+    load8(a.gamma + c, g8);
+    load8(a.beta + c, b8);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float mean = m8[j], var = v8[j];
-      if (!run) {
-        mean *= inv;
-        var = fmaxf(var * inv - mean * mean, 0.f);
-      }
-      const float sc = g8[j] * rsqrtf(var + a.eps);
-      const float sh = b8[j] - mean * sc;
-      acc[j] = pool_act((sc >= 0.f ? acc[j] : mn[j]) * sc + sh, a.act);
+      float sc, sh;
+      bn_scale_shift(m8[j], v8[j], !run, inv, a.eps, g8[j], b8[j], sc, sh);
+      acc[j] = act_fwd((sc >= 0.f ? acc[j] : mn[j]) * sc + sh, a.act);
     }
   }
   bf16x8 o;

@@ -33,7 +33,7 @@
 //     applies the inverse permutation on the SOURCE address (the LDS image is lane-linear).
 #include <stdlib.h>
 
-#include "common.h"
+#include "bn_math.h"
 #include "igemm.h"
 
 namespace {
@@ -534,23 +534,23 @@ int pg_launch(const PgemmArgs& g, const PgemmPro& pro, int grid, hipStream_t st)
   return 0;
 }
 
-// coef[g][0][c] = gamma * rsqrt(var + eps), coef[g][1][c] = beta - mean * scale, from the
-// producer's per-group sums (same arithmetic as bn.hip) or its running statistics
-__global__ __launch_bounds__(256) void pg_coef_kernel(PgemmPro p, int K) {
+// coef[g][0][c] = scale, coef[g][1][c] = shift (bn_math.h), from the producer's per-group sums
+// or its running statistics
+__global__ __launch_bounds__(256) void bn_coef_kernel(PgemmPro p, int K) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= p.G * K) return;
   const int gi = i / K, c = i - gi * K;
   float mean, var;
   if (p.stats) {
-    mean = p.stats[(size_t)gi * 2 * K + c] * p.inv_count;
-    var = fmaxf(p.stats[(size_t)gi * 2 * K + K + c] * p.inv_count - mean * mean, 0.f);
+    bn_mean_var(p.stats[(size_t)gi * 2 * K + c], p.stats[(size_t)gi * 2 * K + K + c], p.inv_count,
+                mean, var);
   } else {
     mean = p.rmean[c];
     var = p.rvar[c];
   }
-  const float sc = p.gamma[c] * rsqrtf(var + p.eps);
+  const float sc = bn_scale(p.gamma[c], var, p.eps);
   p.coef[(size_t)gi * 2 * K + c] = sc;
-  p.coef[(size_t)gi * 2 * K + K + c] = p.beta[c] - mean * sc;
+  p.coef[(size_t)gi * 2 * K + K + c] = bn_shift(p.beta[c], mean, sc);
 }
 
 int pg_cus() {
@@ -566,6 +566,10 @@ int pg_cus() {
 }
 
 }  // namespace
+
+void bn_coef_launch(const PgemmPro& pro, int K, hipStream_t st) {
+  hipLaunchKernelGGL(bn_coef_kernel, dim3((pro.G * K + 255) / 256), dim3(256), 0, st, pro, K);
+}
 
 // returns 0 when the shape / tile is not supported (caller falls back to igemm)
 int pgemm_launch(const PgemmArgs& g_in, int bn, int grid, hipStream_t st, const PgemmPro* pro_in) {
@@ -583,10 +587,7 @@ int pgemm_launch(const PgemmArgs& g_in, int bn, int grid, hipStream_t st, const 
   // CUs to the other stream, whose kernels cannot share a CU with a 130-160 KB LDS block)
   if (grid <= 0) grid = pg_cus();
   if (grid > ntiles) grid = ntiles;
-  if (pro.mode) {
-    const int n = pro.G * g.K;
-    hipLaunchKernelGGL(pg_coef_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pro, g.K);
-  }
+  if (pro.mode) bn_coef_launch(pro, g.K, st);
   switch (bn) {
     case 256: return pg_launch<256, 2, 4, 3, 0>(g, pro, grid, st);
     case 128: return pg_launch<128, 4, 5, 4, 3>(g, pro, grid, st);

@@ -320,23 +320,6 @@ void pw_launch_kb(const PgemmArgs& g, const PgemmPro& pro, hipStream_t st) {
   }
 }
 
-__global__ __launch_bounds__(256) void pw_coef_kernel(PgemmPro p, int K) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= p.G * K) return;
-  const int gi = i / K, c = i - gi * K;
-  float mean, var;
-  if (p.stats) {
-    mean = p.stats[(size_t)gi * 2 * K + c] * p.inv_count;
-    var = fmaxf(p.stats[(size_t)gi * 2 * K + K + c] * p.inv_count - mean * mean, 0.f);
-  } else {
-    mean = p.rmean[c];
-    var = p.rvar[c];
-  }
-  const float sc = p.gamma[c] * rsqrtf(var + p.eps);
-  p.coef[(size_t)gi * 2 * K + c] = sc;
-  p.coef[(size_t)gi * 2 * K + K + c] = p.beta[c] - mean * sc;
-}
-
 }  // namespace
 
 // returns 0 when unsupported: K <= 128 input channels, stride 1, plain or mode-1 prologue,
@@ -349,7 +332,7 @@ int pwconv_launch(const PgemmArgs& g, hipStream_t st, const PgemmPro* pro_in) {
   if (pro.mode == 2) return 0;
   if (pro.mode == 1) {
     if (!pro.coef || pro.G < 1 || pro.group_rows < PW_BM) return 0;
-    hipLaunchKernelGGL(pw_coef_kernel, dim3((pro.G * g.K + 255) / 256), dim3(256), 0, st, pro, g.K);
+    bn_coef_launch(pro, g.K, st);
   }
   switch ((g.K + 31) / 32) {
     case 1: pw_launch_kb<1>(g, pro, st); return 1;

@@ -152,7 +152,7 @@ def bn_bwd_ref(dx, out, y, stats, act, eps=EPS):
 
 # --------------------------------------------------------------------------- integer data
 def case_act(case):
-    """The activation of the BN feeding the conv in a case's ``bw=`` runs (every dw_mask arm)."""
+    """The activation of the BN feeding the conv in a case's ``bw=`` runs (every act_mask arm)."""
     return {16: 'relu', 8: 'none'}.get(case[1], 'relu6')
 
 

@@ -178,3 +178,69 @@ def test_pgemm_input_bn_prologue(case, kern):
     close(ostats, ostats2, rtol=1e-2, atol=0.5)
     assert not torch.isnan(keep.float()).any()
     close(keep.float(), an.float(), rtol=1e-2, atol=1e-2)
+    assert torch.equal(keep, an), '%d of %d elements differ' % ((keep != an).sum().item(),
+                                                                keep.numel())
+
+
+COEF_CASES = [
+    # N, H, W, C, group_imgs, eval
+    # groups of 256 rows: the smallest both launchers accept (pgemm's prologue needs groups of
+    # at least one 256-row tile, pwconv's of one 128-row panel)
+    (4, 8, 8, 24, 0, False),       # one group
+    (8, 8, 8, 24, 4, False),       # two ghost groups
+    (4, 8, 8, 40, 0, True),        # running statistics
+]
+
+
+@pytest.mark.parametrize('case', COEF_CASES)
+def test_coef_workspace_pgemm_equals_pwconv(case):
+    """The scale / shift workspace ([G][2][C]) that the pgemm path (bn = 64) and the pwconv path
+    derive from the same producer statistics is the same to the bit (both reach one kernel through
+    bn_coef_launch), and equals the fp32 formula to the statistics rtol of this file (v_rsq_f32 is
+    not correctly rounded, so no bitwise match with torch is expected)."""
+    from mercury_amd import ops
+    from mercury_amd.ops.conv import ConvSpec
+    ops.lib()
+    N, H, W, C, gimgs, ev = case
+    K = 64
+    g = torch.Generator(device='cpu').manual_seed(11 + C + N)
+    rows = N * H * W
+    yb = (torch.randn(rows, C, generator=g) * 2 + 0.5).to(torch.bfloat16).to(DEV)
+    w = bf(torch.randn(K, C, 1, 1, generator=g) / math.sqrt(C)).to(DEV)
+    gamma = (torch.rand(C, generator=g) + 0.5).to(DEV)
+    beta = (torch.randn(C, generator=g) * 0.3).to(DEV)
+    rmean = (torch.randn(C, generator=g) * 0.2).to(DEV)
+    rvar = (torch.rand(C, generator=g) + 0.5).to(DEV)
+    spec = ConvSpec(N, H, W, C, K, 1, 1, 1, 0)
+    G = N // gimgs if gimgs else 1
+    grp = (gimgs or N) * H * W
+    if gimgs:
+        spec.group_rows = grp
+    yg = yb.float().view(G, grp, C)
+    stats = torch.stack([yg.sum(1), yg.pow(2).sum(1)], 1).contiguous()       # [G][2][C]
+    wk, _ = ops.pack_conv_weight(w)
+    coefs = []
+    for kern in ('pgemm', 'pwconv'):
+        coef = torch.zeros(G * 2 * C, device=DEV)
+        pro = dict(gamma=gamma, beta=beta, act='relu', eps=1e-5, coef=coef, group_rows=grp,
+                   count=grp)
+        if ev:
+            pro.update(rmean=rmean, rvar=rvar)
+        else:
+            pro.update(stats=stats.reshape(-1))
+        out = torch.empty(rows, K, dtype=torch.bfloat16, device=DEV)
+        if kern == 'pwconv':
+            ops.pwconv_fwd(yb, wk, out, spec, pro=pro)
+        else:
+            ops.pgemm_fwd(yb, wk, out, spec, bn=64, pro=pro)
+        coefs.append(coef.view(G, 2, C))
+    assert torch.equal(coefs[0], coefs[1])
+    if ev:
+        mean, var = rmean.view(1, C), rvar.view(1, C)
+    else:
+        mean = stats[:, 0] / grp
+        var = (stats[:, 1] / grp - mean ** 2).clamp_min(0)
+    sc = gamma / torch.sqrt(var + 1e-5)
+    for coef in coefs:
+        close(coef[:, 0], sc.expand(G, C), rtol=1e-2, atol=0)
+        close(coef[:, 1], (beta - mean * sc).expand(G, C), rtol=1e-2, atol=0)
