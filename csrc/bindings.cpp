@@ -619,6 +619,80 @@ PYBIND11_MODULE(_C, m) {
     pool_augment_launch(a, S(st));
     check_launch("pool_augment");
   });
+  // photographic recipes (photo.hip): keyword arguments only
+  m.def("pool_photo", [](uintptr_t shard, uintptr_t labels, uintptr_t ctrl, uintptr_t pool,
+                         uintptr_t pool_label, uintptr_t pool_index, uintptr_t params,
+                         long long params_floats, uintptr_t zero, int nzero, uintptr_t st, int Ns,
+                         int Hs, int Ws, int H, int W, int Pn, int batch, int augment, int shuffle,
+                         uint32_t seed, int flip, std::vector<float> mean,
+                         std::vector<float> inv_std, int cutout, std::vector<float> rrc,
+                         std::vector<float> jitter, int pad, int resize, int Hr, int Wr,
+                         float degrees, float scale_lo, float scale_hi, int affine) {
+    if (Ns < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || Pn < 1 || batch < 1 || pad < 0)
+      throw std::runtime_error("pool_photo: sizes must be positive");
+    if ((long long)H * W * Pn >= (1LL << 30) || (long long)Hs * Ws >= (1LL << 24))
+      throw std::runtime_error("pool_photo: H*W*P must stay below 2^30 and Hs*Ws below 2^24");
+    if (mean.size() != 3 || inv_std.size() != 3)
+      throw std::runtime_error("pool_photo: mean and std have three channels");
+    if (cutout < 0)
+      throw std::runtime_error("pool_photo: cutout >= 0");
+    if (!(rrc.empty() || rrc.size() == 4) || jitter.size() != 4)
+      throw std::runtime_error("pool_photo: rrc is empty or (scale_lo, scale_hi, ratio_lo, "
+                               "ratio_hi), jitter is (brightness, contrast, saturation, hue)");
+    for (float v : jitter)
+      if (!(v >= 0.f) || !std::isfinite(v))
+        throw std::runtime_error("pool_photo: jitter strengths are finite and >= 0");
+    if (jitter[3] > 0.5f)
+      throw std::runtime_error("pool_photo: hue must lie in [0, 0.5]");
+    const bool jit = jitter[0] > 0.f || jitter[1] > 0.f || jitter[2] > 0.f || jitter[3] > 0.f;
+    if (rrc.empty() && !jit)
+      throw std::runtime_error("pool_photo: neither rrc nor jitter is set (pool_augment's case)");
+    if (!rrc.empty()) {
+      for (float v : rrc)
+        if (!std::isfinite(v))
+          throw std::runtime_error("pool_photo: rrc must be finite");
+      if (!(rrc[0] > 0.f) || rrc[1] < rrc[0] || !(rrc[2] > 0.f) || rrc[3] < rrc[2])
+        throw std::runtime_error("pool_photo: rrc needs 0 < scale_lo <= scale_hi and "
+                                 "0 < ratio_lo <= ratio_hi");
+      if (pad || resize || affine || degrees != 0.f || Hr != Hs || Wr != Ws)
+        throw std::runtime_error("pool_photo: rrc replaces resize, pad, degrees and scale");
+    } else {
+      if (resize ? (Hr < 1 || Wr < 1) : (Hr != Hs || Wr != Ws))
+        throw std::runtime_error("pool_photo: resized size does not match the recipe");
+      if (Hr + 2 * pad < H || Wr + 2 * pad < W)
+        throw std::runtime_error("pool_photo: empty crop range (crop larger than the padded image)");
+      if (degrees < 0.f || !(scale_lo > 0.f) || scale_hi < scale_lo)
+        throw std::runtime_error("pool_photo: degrees >= 0, 0 < scale_lo <= scale_hi");
+    }
+    if (params && params_floats != (long long)Pn * 16)
+      throw std::runtime_error("pool_photo: params must hold P * 16 floats");
+    PoolPhotoArgs a{{{P<const uint8_t>(shard), P<const int64_t>(labels), P<const int64_t>(ctrl),
+                      P<bf16>(pool), P<int>(pool_label), P<int>(pool_index), Ns, H, W, Pn, batch,
+                      pad, flip, augment, shuffle, seed, {mean[0], mean[1], mean[2]},
+                      {inv_std[0], inv_std[1], inv_std[2]}, 0, P<float>(zero), nzero},
+                     Hs, Ws, resize, Hr, Wr, degrees, scale_lo, scale_hi, cutout, affine, nullptr},
+                    rrc.empty() ? 0 : 1, 1.f, 1.f, 1.f, 1.f, 0.f, 0.f,
+                    {jitter[0], jitter[1], jitter[2], jitter[3]}, P<float>(params)};
+    if (!rrc.empty()) {
+      a.scale_lo = rrc[0];
+      a.scale_hi = rrc[1];
+      a.ratio_lo = rrc[2];
+      a.ratio_hi = rrc[3];
+      a.log_ratio_lo = (float)std::log((double)rrc[2]);
+      a.log_ratio_hi = (float)std::log((double)rrc[3]);
+    }
+    pool_photo_launch(a, S(st));
+    check_launch("pool_photo");
+  }, py::kw_only(), py::arg("shard"), py::arg("labels"), py::arg("ctrl"), py::arg("pool"),
+     py::arg("pool_label"), py::arg("pool_index"), py::arg("params") = 0,
+     py::arg("params_floats") = 0, py::arg("zero") = 0, py::arg("nzero") = 0, py::arg("stream"),
+     py::arg("Ns"), py::arg("Hs"), py::arg("Ws"), py::arg("H"), py::arg("W"), py::arg("P"),
+     py::arg("batch"), py::arg("augment"), py::arg("shuffle"), py::arg("seed"), py::arg("flip"),
+     py::arg("mean"), py::arg("inv_std"), py::arg("cutout") = 0,
+     py::arg("rrc") = std::vector<float>(), py::arg("jitter") = std::vector<float>(4, 0.f),
+     py::arg("pad") = 0, py::arg("resize") = 0, py::arg("Hr"), py::arg("Wr"),
+     py::arg("degrees") = 0.f, py::arg("scale_lo") = 1.f, py::arg("scale_hi") = 1.f,
+     py::arg("affine") = 0);
   m.def("pool_spec", [](uintptr_t shard, uintptr_t labels, uintptr_t ctrl, uintptr_t pool,
                         uintptr_t pool_label, uintptr_t pool_index, int Ns, int C, int H, int W,
                         int Pn, int batch, int augment, int shuffle, uint32_t seed, uintptr_t st,

@@ -16,32 +16,12 @@
 // (the global importance table of Groupwise_Sampler lives in table.hip)
 #include "common.h"
 #include "kernels.h"
+#include "pool_geom.h"
 
 namespace {
 
-// Which shard sample fills pool slot `slot` (epoch permutation, drop_last batches), and the
-// global batch number gb that seeds its augmentation.
-MA_DEV uint32_t pool_src(const PoolBuildArgs& a, int slot, int64_t& gb, int& t) {
-  const int j = slot / a.batch;
-  t = slot - j * a.batch;
-  const int64_t pc = a.ctrl[0];
-  const int per_pool = a.P / a.batch;
-  const int nb = max(1, a.Ns / a.batch);
-  gb = pc * per_pool + j;
-  const uint32_t epoch = (uint32_t)(gb / nb);
-  const int bi = (int)(gb % nb);
-  // (% Ns only matters for a shard smaller than one batch: the batch cycles the shard)
-  const uint32_t pos = (uint32_t)((bi * a.batch + t) % a.Ns);
-  return a.shuffle ? permute_index(pos, (uint32_t)a.Ns, a.seed, epoch)
-                   : (uint32_t)((gb * a.batch + t) % a.Ns);
-}
-
 // Pre-converted shard (non-image inputs, e.g. the speech VGG's 1x101x161 spectrograms, stored
 // once as NHWC bf16 with channels padded to 8): the pool is a straight 16-byte-chunk gather.
-MA_DEV void zero_slice(const PoolBuildArgs& a) {
-  for (int j = blockIdx.x * 256 + threadIdx.x; j < a.nzero; j += gridDim.x * 256) a.zero[j] = 0.f;
-}
-
 __global__ __launch_bounds__(256) void pool_take_kernel(PoolBuildArgs a) {
   const int slot = blockIdx.x;
   if (a.zero) zero_slice(a);
@@ -100,37 +80,7 @@ __global__ __launch_bounds__(256) void pool_build_kernel(PoolBuildArgs a) {
 }
 
 // ---- augmentation recipes (PoolAugmentArgs) ------------------------------------------------
-// Tap (y, x) of the cropped view, 0 <= y < H, 0 <= x < W: undo the flip, move into the padded
-// resized image, zero in the padding; the resized image itself is torch's bilinear with
-// align_corners=False over the uint8 source, every source index clamped into the image.
-template <bool RESIZE>
-MA_DEV void aug_tap(const PoolAugmentArgs& a, const uint8_t* img, int y, int x, int dy, int dx,
-                    int flip, float ry, float rx, float v[3]) {
-  const int xc = flip ? (a.b.W - 1 - x) : x;
-  const int ys = y + dy - a.b.pad, xs = xc + dx - a.b.pad;
-  v[0] = v[1] = v[2] = 0.f;
-  if (ys < 0 || xs < 0 || ys >= a.Hr || xs >= a.Wr) return;
-  if (!RESIZE) {               // (Hr, Wr) == (Hs, Ws), checked by the binding
-    const uint8_t* p = img + ((size_t)ys * a.Ws + xs) * 3;
-    v[0] = p[0];
-    v[1] = p[1];
-    v[2] = p[2];
-    return;
-  }
-  const float fy = fmaxf((ys + 0.5f) * ry - 0.5f, 0.f), fx = fmaxf((xs + 0.5f) * rx - 0.5f, 0.f);
-  const int y0 = min((int)fy, a.Hs - 1), x0 = min((int)fx, a.Ws - 1);
-  const int y1 = min(y0 + 1, a.Hs - 1), x1 = min(x0 + 1, a.Ws - 1);
-  const float ly = fy - y0, lx = fx - x0;
-  const uint8_t* p0 = img + (size_t)y0 * a.Ws * 3;
-  const uint8_t* p1 = img + (size_t)y1 * a.Ws * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float top = p0[x0 * 3 + c] * (1.f - lx) + p0[x1 * 3 + c] * lx;
-    const float bot = p1[x0 * 3 + c] * (1.f - lx) + p1[x1 * 3 + c] * lx;
-    v[c] = top * (1.f - ly) + bot * ly;
-  }
-}
-
+// (pool_src, zero_slice and the per-tap geometry aug_tap: pool_geom.h, shared with photo.hip)
 // One block per pool slot, like pool_build_kernel, whose crop / flip draw (first Philox call)
 // this repeats word for word: a crop-and-flip recipe on a shard of the output size gives the
 // same bits from either kernel.
@@ -233,7 +183,8 @@ __global__ __launch_bounds__(256) void pool_augment_kernel(PoolAugmentArgs a) {
 // gain is exactly 1.0f when unset, so values pass through bit for bit.  Channels C..7 are +0.
 //
 // Draws per slot: Philox on the counter (gb, t) of the image kernels, stream words 0x5bec0..2
-// (the image kernels use 0x5eed and 0x5eee):
+// (the image kernels use 0x5eed: dy, dx, flip and 0x5eee: angle, scale, cut_y, cut_x; photo.hip
+// adds 0x5ef0..0x5ef4: box attempts, 0x5ef5: top, left, 0x5ef8: colour factors, 0x5ef9: order):
 //   0x5bec0: .x shift   .y gain      .z width fa   .w start fa
 //   0x5bec1: .x width fb  .y start fb  .z width ta   .w start ta
 //   0x5bec2: .x width tb  .y start tb

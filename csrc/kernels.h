@@ -161,6 +161,23 @@ struct PoolAugmentArgs {
 };
 void pool_augment_launch(const PoolAugmentArgs& a, hipStream_t st);
 
+// Photographic recipe (AugmentRecipe with rrc or jitter, photo.hip): geometry -> flip ->
+// ColorJitter -> /255 -> Normalize -> Cutout.  The geometry is either PoolAugmentArgs' chain or
+// RandomResizedCrop (a drawn box of the source, bilinear to b.H x b.W, no antialiasing).
+struct PoolPhotoArgs {
+  PoolAugmentArgs a;             // a.b as in the sibling kernels; with rrc: a.b.pad = 0, no resize,
+                                 // no affine, (a.Hr, a.Wr) = (a.Hs, a.Ws); a.params is unused
+  int rrc;                       // RandomResizedCrop replaces Resize / RandomCrop / RandomAffine
+  float scale_lo, scale_hi;      // box area as a fraction of the source, drawn from [lo, hi)
+  float ratio_lo, ratio_hi;      // box aspect w / h, log-uniform in [lo, hi)
+  float log_ratio_lo, log_ratio_hi;
+  float jitter[4];               // brightness, contrast, saturation, hue strengths (0: off)
+  float* params;                 // optional [P][16]: [0..7] PoolAugmentArgs' layout (rrc: top, left,
+                                 // flip, 0, 1, cut_y, cut_x, attempt), box h, w, fb, fc, fs, fh,
+                                 // order code, grey mean used by contrast
+};
+void pool_photo_launch(const PoolPhotoArgs& p, hipStream_t st);
+
 // Spectrogram recipe (mercury_amd/data/augment.py, SpecRecipe): time shift -> gain -> frequency
 // and time masks in output coordinates, from a PLANAR bf16 shard to the NHWC8 pool.
 struct PoolSpecArgs {

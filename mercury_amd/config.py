@@ -40,6 +40,8 @@ class Config:
     #                                 flip + CIFAR Normalize) | 'dataset' (read from the loaders'
     #                                 dataset.transform) | an AugmentRecipe.parse spec, e.g.
     #                                 'resize=35,crop=32,flip=1,degrees=10,scale=0.9:1.1,norm=none'
+    #                                 or 'crop=224,flip=1,rrc=0.08:1.0/0.75:1.3333,
+    #                                 jitter=0.4:0.4:0.4:0.1' (RandomResizedCrop, ColorJitter)
     #                                 | a SpecRecipe.parse spec for float [N][C][F][T] datasets,
     #                                 e.g. 'spec:shift=8,fmask=2x10,tmask=2x20,gain=0.8:1.2'
     # model / optimisation

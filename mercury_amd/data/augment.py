@@ -24,6 +24,31 @@ GPU tests compare against.  Per output pixel (i, j) of the H x W crop:
 Values stay float between the stages.  The CPU transforms round to uint8 after ``Resize``
 and after ``RandomAffine``; the unrounded result is within one uint8 level of theirs.
 
+Photographic recipes add two optional fields (``pool_photo_kernel``, ``csrc/photo.hip``; params
+are then ``PHOTO_PARAMS`` = 16 values per slot):
+
+    RandomResizedCrop | the geometry above -> [flip] -> [ColorJitter] -> /255 -> [Normalize]
+                      -> [Cutout]
+
+* ``rrc = (scale_lo, scale_hi, ratio_lo, ratio_hi)``: ``RandomResizedCrop`` to ``crop``, in the
+  place of Resize, RandomCrop, padding and RandomAffine.  The box is torchvision's
+  ``get_params``: up to 10 attempts of ``target = Hs*Ws * U(scale)``, ``aspect = exp(U(log
+  ratio))``, ``w = round(sqrt(target*aspect))``, ``h = round(sqrt(target/aspect))``, the first
+  with ``0 < w <= Ws`` and ``0 < h <= Hs`` wins, ``top = r % (Hs-h+1)``, ``left = r' % (Ws-w+1)``;
+  else the whole image clipped to the ratio range, centred (``fallback_box``).  The box is
+  resized bilinearly with ``align_corners=False`` and NO antialiasing: ``fy = max((i+0.5)*h/H -
+  0.5, 0)``, rows ``y0 = min(floor(fy), h-1)`` and ``min(y0+1, h-1)`` relative to the box (indices
+  clamp at the box edge, the crop comes first), columns likewise from ``W-1-j`` when flipped; the
+  taps are read at ``top + y``, ``left + x``.
+* ``jitter = (brightness, contrast, saturation, hue)``: ``ColorJitter`` (torchvision's tensor
+  path) on the [0, 1] values after ``/255``, with either geometry; the padding of the old
+  geometry is black pixels of the image and takes part.  ``grey(v) = 0.299 r + 0.587 g + 0.114
+  b``; brightness ``clamp(v*fb, 0, 1)``; contrast ``clamp(fc*v + (1-fc)*m, 0, 1)`` with ``m`` the
+  mean of ``grey`` over the H x W image as it stands when contrast runs; saturation ``clamp(fs*v
+  + (1-fs)*grey(v), 0, 1)``; hue RGB -> HSV, ``h <- (h + fh) mod 1``, HSV -> RGB.  ``fb, fc, fs ~
+  U[max(0, 1-x), 1+x]``, ``fh ~ U[-hue, hue]``.  The four run in a per-slot order, one of 24
+  (``jitter_order``); a strength of 0 skips that operation in place.
+
 ``SpecRecipe`` (below) is the recipe of float spectrogram inputs: time shift, gain, frequency
 and time masks, run by ``pool_spec_kernel`` from a planar bf16 shard and exact to the bit.
 """
@@ -55,6 +80,9 @@ class AugmentRecipe:
     cutout: int = 0
     mean: Optional[Tuple[float, ...]] = None  # None: no Normalize (mean 0, std 1)
     std: Optional[Tuple[float, ...]] = None
+    rrc: Optional[Tuple[float, float, float, float]] = None     # scale lo, hi; ratio lo, hi
+    jitter: Optional[Tuple[float, float, float, float]] = None  # brightness, contrast,
+    #                                                             saturation, hue strengths
 
     def __post_init__(self):
         s = object.__setattr__
@@ -78,6 +106,33 @@ class AugmentRecipe:
             raise ValueError('AugmentRecipe: resize, pad, cutout and degrees are >= 0')
         if self.scale is not None and not 0 < self.scale[0] <= self.scale[1]:
             raise ValueError('AugmentRecipe: scale is (lo, hi) with 0 < lo <= hi')
+        if self.rrc is not None:
+            if len(self.rrc) != 4:
+                raise ValueError('AugmentRecipe: rrc is (scale_lo, scale_hi, ratio_lo, ratio_hi)')
+            s(self, 'rrc', tuple(float(v) for v in self.rrc))
+            clash = [n for n, on in (('resize', self.resize), ('pad', self.pad),
+                                     ('degrees', self.degrees), ('scale', self.scale is not None))
+                     if on]
+            if clash:
+                raise ValueError('AugmentRecipe: rrc replaces Resize, RandomCrop and RandomAffine; '
+                                 'it cannot be combined with %s' % ', '.join(clash))
+            slo, shi, rlo, rhi = self.rrc
+            if not all(math.isfinite(v) for v in self.rrc) or not (0 < slo <= shi and
+                                                                   0 < rlo <= rhi):
+                raise ValueError('AugmentRecipe: rrc needs 0 < scale_lo <= scale_hi and '
+                                 '0 < ratio_lo <= ratio_hi, got %r' % (self.rrc,))
+        if self.jitter is not None:
+            if len(self.jitter) != 4:
+                raise ValueError('AugmentRecipe: jitter is (brightness, contrast, saturation, hue)')
+            s(self, 'jitter', tuple(float(v) for v in self.jitter))
+            if not all(math.isfinite(v) and v >= 0 for v in self.jitter):
+                raise ValueError('AugmentRecipe: jitter strengths are >= 0, got %r'
+                                 % (self.jitter,))
+            if self.jitter[3] > 0.5:
+                raise ValueError('AugmentRecipe: jitter hue lies in [0, 0.5], got %r'
+                                 % self.jitter[3])
+            if not any(self.jitter):
+                s(self, 'jitter', None)
 
     # ---------------------------------------------------------------- constructors
     @classmethod
@@ -94,8 +149,9 @@ class AugmentRecipe:
         if not isinstance(t, T.Compose):
             raise ValueError('AugmentRecipe.from_transform: expected a transforms.Compose, got %r'
                              % (t,))
-        order = [T.ToPILImage, T.Resize, T.RandomCrop, T.RandomHorizontalFlip, T.RandomAffine,
-                 T.ToTensor, T.Normalize, T.Cutout]
+        order = [T.ToPILImage, T.Resize, T.RandomCrop, T.RandomResizedCrop,
+                 T.RandomHorizontalFlip, T.RandomAffine, T.ColorJitter, T.ToTensor, T.Normalize,
+                 T.Cutout]
         kw, pos, seen_tensor = {}, 0, False
         for tr in t.transforms:
             k = next((i for i in range(pos, len(order)) if type(tr) is order[i]), None)
@@ -108,6 +164,14 @@ class AugmentRecipe:
                 kw['resize'] = tr.size
             elif isinstance(tr, T.RandomCrop):
                 kw['crop'], kw['pad'] = _pair(tr.size), tr.padding
+            elif isinstance(tr, T.RandomResizedCrop):
+                if 'crop' in kw:
+                    raise ValueError('AugmentRecipe.from_transform: %r after a RandomCrop '
+                                     '(RandomResizedCrop stands in the place of Resize and '
+                                     'RandomCrop)' % (tr,))
+                kw['crop'], kw['rrc'] = _pair(tr.size), tuple(tr.scale) + tuple(tr.ratio)
+            elif isinstance(tr, T.ColorJitter):
+                kw['jitter'] = (tr.brightness, tr.contrast, tr.saturation, tr.hue)
             elif isinstance(tr, T.RandomHorizontalFlip):
                 if tr.p != 0.5:
                     raise ValueError('AugmentRecipe.from_transform: %r with p=%r (only p=0.5 is '
@@ -132,7 +196,9 @@ class AugmentRecipe:
     @classmethod
     def parse(cls, spec):
         """``resize=35,crop=32,flip=1,degrees=10,scale=0.9:1.1,cutout=0,norm=none``; ``crop`` is
-        ``32`` or ``24x32``, ``norm`` is ``cifar``, ``none`` or ``m0:m1:m2/s0:s1:s2``."""
+        ``32`` or ``24x32``, ``norm`` is ``cifar``, ``none`` or ``m0:m1:m2/s0:s1:s2``.  The
+        photographic keys: ``rrc=0.08:1.0/0.75:1.3333`` (scale lo:hi / ratio lo:hi) and
+        ``jitter=0.4:0.4:0.4:0.1`` (brightness:contrast:saturation:hue); ``none`` unsets either."""
         kw = {}
         for item in spec.split(','):
             if '=' not in item:
@@ -150,6 +216,29 @@ class AugmentRecipe:
                 kw[k] = None if v in ('', 'none') else tuple(float(x) for x in v.split(':'))
                 if kw[k] is not None and len(kw[k]) != 2:
                     raise ValueError('AugmentRecipe.parse: scale is lo:hi')
+            elif k == 'rrc':
+                if v in ('', 'none'):
+                    kw[k] = None
+                    continue
+                sc, sep, ra = v.partition('/')
+                try:
+                    kw[k] = tuple(float(x) for x in sc.split(':') + ra.split(':'))
+                except ValueError:
+                    kw[k] = ()
+                if not sep or len(sc.split(':')) != 2 or len(kw[k]) != 4:
+                    raise ValueError('AugmentRecipe.parse: rrc is scale_lo:scale_hi/ratio_lo:'
+                                     'ratio_hi, got %r' % v)
+            elif k == 'jitter':
+                if v in ('', 'none'):
+                    kw[k] = None
+                    continue
+                try:
+                    kw[k] = tuple(float(x) for x in v.split(':'))
+                except ValueError:
+                    kw[k] = ()
+                if len(kw[k]) != 4:
+                    raise ValueError('AugmentRecipe.parse: jitter is brightness:contrast:'
+                                     'saturation:hue, got %r' % v)
             elif k == 'norm':
                 if v == 'cifar':
                     kw['mean'], kw['std'] = CIFAR_MEAN, CIFAR_STD
@@ -175,6 +264,10 @@ class AugmentRecipe:
         else:
             out.append('norm=%s/%s' % (':'.join(repr(m) for m in self.mean),
                                        ':'.join(repr(s) for s in self.std)))
+        if self.rrc is not None:
+            out.append('rrc=%r:%r/%r:%r' % self.rrc)
+        if self.jitter is not None:
+            out.append('jitter=%r:%r:%r:%r' % self.jitter)
         return ','.join(out)
 
     # ---------------------------------------------------------------- geometry
@@ -185,6 +278,11 @@ class AugmentRecipe:
     @property
     def affine(self):
         return self.degrees != 0 or self.scale is not None
+
+    @property
+    def photo(self):
+        """``rrc`` or ``jitter`` is set: ``pool_photo_kernel``'s case, ``PHOTO_PARAMS`` draws."""
+        return self.rrc is not None or self.jitter is not None
 
     def with_crop(self, hw):
         """This recipe with ``crop`` filled in where the Compose had no RandomCrop."""
@@ -204,6 +302,11 @@ class AugmentRecipe:
             raise ValueError('AugmentRecipe: crop is unset (with_crop)')
         Hr, Wr = self.resized_hw(Hs, Ws)
         H, W = self.crop
+        if self.rrc is not None:         # any box of any source resizes to the crop
+            if min(H, W, Hs, Ws) < 1:
+                raise ValueError('AugmentRecipe: empty crop %dx%d or source %dx%d'
+                                 % (H, W, Hs, Ws))
+            return
         if min(H, W, Hr, Wr) < 1 or Hr + 2 * self.pad < H or Wr + 2 * self.pad < W:
             raise ValueError('AugmentRecipe: crop %dx%d does not fit the %dx%d image (source '
                              '%dx%d, resize %d) with padding %d'
@@ -211,16 +314,64 @@ class AugmentRecipe:
 
     def is_legacy(self, Hs, Ws):
         """Crop-with-pad and flip on a shard of the output size: ``pool_build_kernel``'s case."""
-        return (not self.resize and not self.affine and not self.cutout
+        return (not self.resize and not self.affine and not self.cutout and not self.photo
                 and self.crop == (Hs, Ws))
 
     def norm(self):
         return (self.mean or (0.0, 0.0, 0.0)), (self.std or (1.0, 1.0, 1.0))
 
+    def fallback_box(self, Hs, Ws):
+        """``(top, left, h, w)`` when all ten attempts fail, and with ``augment=False``: the
+        whole image clipped to the ratio range, centred (torchvision's fallback)."""
+        _, _, rlo, rhi = self.rrc
+        h, w = Hs, Ws
+        if Ws / Hs < rlo:
+            h = min(max(int(round(Ws / rlo)), 1), Hs)
+        elif Ws / Hs > rhi:
+            w = min(max(int(round(Hs * rhi)), 1), Ws)
+        return (Hs - h) // 2, (Ws - w) // 2, h, w
+
+    @staticmethod
+    def jitter_order(code):
+        """The order of (0 brightness, 1 contrast, 2 saturation, 3 hue) that order code 0..23
+        stands for, its Lehmer code: from [0, 1, 2, 3] take element ``code // 6``, then element
+        ``code % 6 // 2`` of the rest, then element ``code % 2``, then what is left."""
+        code = int(code)
+        if not 0 <= code < 24:
+            raise ValueError('jitter_order: code is 0..23, got %r' % code)
+        rest = [0, 1, 2, 3]
+        return [rest.pop(code // 6), rest.pop(code % 6 // 2), rest.pop(code % 2), rest[0]]
+
+    def _jitter(self, x, params, info=None):
+        """ColorJitter on [H][W][3] values in [0, 1] with the factors and the order code of
+        ``params[10:15]`` (module docstring); the grey mean is this image's own."""
+        f = [float(v) for v in params[10:14]]
+        wts = torch.tensor([0.299, 0.587, 0.114], dtype=x.dtype)
+        for op in self.jitter_order(params[14]):
+            if not self.jitter[op]:
+                continue
+            if op == 0:
+                x = (x * f[0]).clamp(0, 1)
+            elif op == 1:
+                m = (x * wts).sum(-1).mean()
+                if info is not None:
+                    info['grey_mean'] = float(m)
+                x = (f[1] * x + (1 - f[1]) * m).clamp(0, 1)
+            elif op == 2:
+                x = (f[2] * x + (1 - f[2]) * (x * wts).sum(-1, keepdim=True)).clamp(0, 1)
+            else:
+                x = _adjust_hue(x, f[3])
+        return x
+
     # ---------------------------------------------------------------- CPU reference
-    def reference(self, img_u8, params, dtype=torch.float64):
+    def reference(self, img_u8, params, dtype=torch.float64, info=None):
         """The recipe on one HWC uint8 image with explicit draws ``params = (dy, dx, flip,
-        angle_deg, scale, cut_y, cut_x)`` -> [H][W][3] ``dtype`` (module docstring)."""
+        angle_deg, scale, cut_y, cut_x)`` -> [H][W][3] ``dtype`` (module docstring).  A recipe
+        with ``rrc`` or ``jitter`` takes the ``PHOTO_PARAMS`` form: ``[0..7]`` as above (``rrc``:
+        top, left, flip, 0, 1, cut_y, cut_x, attempt), ``[8], [9]`` the box h, w, ``[10..13]``
+        fb, fc, fs, fh, ``[14]`` the order code; ``[15]`` (the kernel's grey mean) is never read: the
+        contrast step takes the mean of its own pixels, and leaves it in ``info['grey_mean']``
+        when ``info`` is a dict."""
         src = torch.as_tensor(img_u8)
         if src.dim() != 3 or src.shape[2] != 3:
             raise ValueError('reference: image must be [H][W][3]')
@@ -230,6 +381,9 @@ class AugmentRecipe:
         Hr, Wr = self.resized_hw(Hs, Ws)
         H, W = self.crop
         pad = self.pad
+        if self.photo and len(params) != PHOTO_PARAMS:
+            raise ValueError('reference: a recipe with rrc or jitter takes %d params, got %d'
+                             % (PHOTO_PARAMS, len(params)))
         dy, dx, flip = int(params[0]), int(params[1]), bool(int(params[2]))
         angle, scale = float(params[3]), float(params[4])
         cut_y, cut_x = int(params[5]), int(params[6])
@@ -255,8 +409,27 @@ class AugmentRecipe:
             v = resized(ys.clamp(0, Hr - 1), xs.clamp(0, Wr - 1))
             return v * ok.unsqueeze(-1).to(dtype)
 
+        def box(i, j):                  # RandomResizedCrop: the resized box at (i, j)
+            top, left, bh, bw = dy, dx, int(params[8]), int(params[9])
+            if not (1 <= bh and 1 <= bw and 0 <= top and 0 <= left
+                    and top + bh <= Hs and left + bw <= Ws):
+                raise ValueError('reference: box %r leaves the %dx%d image'
+                                 % ((top, left, bh, bw), Hs, Ws))
+            jx = W - 1 - j if flip else j
+            fy = ((i.to(dtype) + 0.5) * (bh / H) - 0.5).clamp(min=0)
+            fx = ((jx.to(dtype) + 0.5) * (bw / W) - 0.5).clamp(min=0)
+            y0 = fy.floor().long().clamp(max=bh - 1)
+            x0 = fx.floor().long().clamp(max=bw - 1)
+            y1, x1 = (y0 + 1).clamp(max=bh - 1), (x0 + 1).clamp(max=bw - 1)
+            ly, lx = (fy - y0).unsqueeze(-1), (fx - x0).unsqueeze(-1)
+            up = src[top + y0, left + x0] * (1 - lx) + src[top + y0, left + x1] * lx
+            lo = src[top + y1, left + x0] * (1 - lx) + src[top + y1, left + x1] * lx
+            return up * (1 - ly) + lo * ly
+
         i, j = torch.meshgrid(torch.arange(H), torch.arange(W), indexing='ij')
-        if self.affine:
+        if self.rrc is not None:
+            v = box(i, j)
+        elif self.affine:
             xn = (2 * j + 1).to(dtype) / W - 1
             yn = (2 * i + 1).to(dtype) / H - 1
             c, s = math.cos(math.radians(angle)) / scale, math.sin(math.radians(angle)) / scale
@@ -270,7 +443,10 @@ class AugmentRecipe:
         else:
             v = tap(i, j)
         mean, std = self.norm()
-        out = (v / 255 - torch.tensor(mean, dtype=dtype)) / torch.tensor(std, dtype=dtype)
+        v = v / 255
+        if self.jitter is not None:
+            v = self._jitter(v, params, info)
+        out = (v - torch.tensor(mean, dtype=dtype)) / torch.tensor(std, dtype=dtype)
         if self.cutout:
             h = self.cutout // 2
             y1, y2 = min(max(cut_y - h, 0), H), min(max(cut_y + h, 0), H)
@@ -279,8 +455,40 @@ class AugmentRecipe:
         return out
 
 
+def _adjust_hue(x, fh):
+    """torchvision's ``adjust_hue`` on [..][3] RGB in [0, 1]: RGB -> HSV, ``h <- (h + fh) mod
+    1``, HSV -> RGB (``_rgb2hsv`` / ``_hsv2rgb`` of its tensor path)."""
+    r, g, b = x.unbind(-1)
+    maxc, minc = x.max(-1).values, x.min(-1).values
+    eqc = maxc == minc
+    cr = maxc - minc
+    ones = torch.ones_like(maxc)
+    s = cr / torch.where(eqc, ones, maxc)
+    div = torch.where(eqc, ones, cr)
+    rc, gc, bc = (maxc - r) / div, (maxc - g) / div, (maxc - b) / div
+    isr, isg = maxc == r, maxc == g
+    h = torch.where(isr, bc - gc, torch.where(isg, 2.0 + rc - bc, 4.0 + gc - rc))
+    h = h / 6.0 + 1.0
+    h = h - h.floor()
+    h = h + fh
+    h = h - h.floor()
+    h6 = h * 6.0
+    i = h6.floor()
+    f = h6 - i
+    i = i.long() % 6
+    p = (maxc * (1.0 - s)).clamp(0, 1)
+    q = (maxc * (1.0 - f * s)).clamp(0, 1)
+    t = (maxc * (1.0 - s * (1.0 - f))).clamp(0, 1)
+    pick = i.unsqueeze(-1)
+    out = [torch.stack(a, -1).gather(-1, pick).squeeze(-1)
+           for a in ((maxc, q, p, p, t, maxc), (t, maxc, maxc, q, p, p), (p, p, t, maxc, maxc, q))]
+    return torch.stack(out, -1)
+
+
 # ---------------------------------------------------------------------- spectrograms
 SPEC_PARAMS = 12     # shift, gain, f0a, fwa, f0b, fwb, t0a, twa, t0b, twb, 0, 0
+PHOTO_PARAMS = 16    # AugmentRecipe with rrc or jitter: dy|top, dx|left, flip, angle_deg, scale,
+#                      cut_y, cut_x, attempt, box h, box w, fb, fc, fs, fh, order code, grey mean
 
 
 def _mask(v, name):

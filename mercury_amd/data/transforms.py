@@ -10,7 +10,9 @@ On the GPU hot path none of these objects run.  ``mercury_amd.ops.pool_build``
 builds a whole presample pool in one HIP kernel from the HBM-resident uint8 shard:
 by default RandomCrop(pad 4) + flip + CIFAR Normalize, or, given an
 ``AugmentRecipe`` (``data/augment.py``), the pipeline that recipe describes --
-Resize, RandomCrop, RandomHorizontalFlip, RandomAffine, Normalize, Cutout.
+Resize, RandomCrop, RandomHorizontalFlip, RandomAffine, Normalize, Cutout, and the
+photographic pair RandomResizedCrop and ColorJitter (``pool_photo_kernel``), whose
+classes here run the recipe's own reference arithmetic.
 ``AugmentRecipe.from_transform`` reads a ``Compose`` of the classes below into a
 recipe (``Config.augment = 'dataset'``), so the native engine applies what the
 dataset's transform says; the kernel keeps values in float between the stages,
@@ -28,6 +30,8 @@ import torch.nn.functional as F
 
 CIFAR_MEAN = [0.49139968, 0.48215827, 0.44653124]
 CIFAR_STD = [0.24703233, 0.24348505, 0.26158768]
+IMAGENET_MEAN = [0.485, 0.456, 0.406]
+IMAGENET_STD = [0.229, 0.224, 0.225]
 
 
 class Compose(object):
@@ -182,6 +186,84 @@ class Cutout(object):
         return img * torch.from_numpy(mask).expand_as(img)
 
 
+def _to_u8(ref):
+    """``AugmentRecipe.reference`` output without Normalize ([0, 1]) -> HWC uint8 array."""
+    return (ref * 255).clamp(0, 255).round().byte().numpy()
+
+
+class RandomResizedCrop(object):
+    """A random box of the image (area fraction in ``scale``, aspect log-uniform in ``ratio``,
+    torchvision's ``get_params`` with its fallback) resized to ``size``, bilinear, no
+    antialiasing, on an HWC uint8 array.  The draws come from numpy's global RNG; the arithmetic
+    is ``AugmentRecipe.reference`` (``data/augment.py``) in fp64, rounded to uint8, so this and
+    the native engine's pool build agree on what the transform means.  ``last``: the last
+    call's draws in the recipe's 16-value params layout."""
+
+    def __init__(self, size, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
+        from .augment import AugmentRecipe
+        self.size = size
+        self.scale = (float(scale[0]), float(scale[1]))
+        self.ratio = (float(ratio[0]), float(ratio[1]))
+        self.recipe = AugmentRecipe(crop=size, rrc=self.scale + self.ratio)
+        self.last = None
+
+    def get_params(self, Hs, Ws):
+        """``(top, left, h, w, attempt)``; attempt 10 is the fallback box."""
+        lo, hi = math.log(self.ratio[0]), math.log(self.ratio[1])
+        for attempt in range(10):
+            target = Hs * Ws * np.random.uniform(*self.scale)
+            aspect = math.exp(np.random.uniform(lo, hi))
+            w, h = int(round(math.sqrt(target * aspect))), int(round(math.sqrt(target / aspect)))
+            if 0 < w <= Ws and 0 < h <= Hs:
+                return (np.random.randint(0, Hs - h + 1), np.random.randint(0, Ws - w + 1), h, w,
+                        attempt)
+        return self.recipe.fallback_box(Hs, Ws) + (10,)
+
+    def __call__(self, x):
+        x = np.ascontiguousarray(_as_hwc(x))
+        top, left, h, w, attempt = self.get_params(x.shape[0], x.shape[1])
+        self.last = [float(top), float(left), 0.0, 0.0, 1.0, 0.0, 0.0, float(attempt), float(h),
+                     float(w), 1.0, 1.0, 1.0, 0.0, 0.0, 0.0]
+        return _to_u8(self.recipe.reference(x, self.last))
+
+    def __repr__(self):
+        return 'RandomResizedCrop(size=%r, scale=%r, ratio=%r)' % (self.size, self.scale,
+                                                                   self.ratio)
+
+
+class ColorJitter(object):
+    """Brightness, contrast, saturation and hue in a random order (torchvision's tensor-path
+    arithmetic) on an HWC uint8 array; each argument is a strength ``x``: the factor is drawn
+    from ``[max(0, 1 - x), 1 + x]``, the hue shift from ``[-hue, hue]``, the order is one of 24
+    (``AugmentRecipe.jitter_order``).  Draws from numpy's global RNG, arithmetic of
+    ``AugmentRecipe.reference`` in fp64, rounded to uint8; ``last`` as in RandomResizedCrop."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0):
+        from .augment import AugmentRecipe
+        self.brightness, self.contrast = float(brightness), float(contrast)
+        self.saturation, self.hue = float(saturation), float(hue)
+        # (validates the strengths; all four zero is the identity)
+        self.recipe = AugmentRecipe(jitter=(self.brightness, self.contrast, self.saturation,
+                                            self.hue))
+        self.last = None
+
+    def __call__(self, x):
+        x = np.ascontiguousarray(_as_hwc(x))
+        f = [np.random.uniform(max(0.0, 1.0 - s), 1.0 + s)
+             for s in (self.brightness, self.contrast, self.saturation)]
+        f.append(np.random.uniform(-self.hue, self.hue))
+        code = int(np.random.randint(24))
+        self.last = [0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0] + \
+            [float(v) for v in f] + [float(code), 0.0]
+        if self.recipe.jitter is None:
+            return x
+        return _to_u8(self.recipe.with_crop(x.shape[:2]).reference(x, self.last))
+
+    def __repr__(self):
+        return 'ColorJitter(brightness=%r, contrast=%r, saturation=%r, hue=%r)' % (
+            self.brightness, self.contrast, self.saturation, self.hue)
+
+
 class SpecAugment(object):
     """A ``SpecRecipe`` (``data/augment.py``: time shift, gain, frequency and time masks) on one
     float [C][F][T] tensor: the draws come from torch's RNG (``generator``, default the global
@@ -216,6 +298,12 @@ def cifar_train_transform():
 
 def cifar_test_transform():
     return Compose([ToPILImage(), ToTensor(), Normalize(CIFAR_MEAN, CIFAR_STD)])
+
+
+def imagenet_train_transform(size=224):
+    """The usual ImageNet training pipeline: RandomResizedCrop, flip, ImageNet Normalize."""
+    return Compose([ToPILImage(), RandomResizedCrop(size), RandomHorizontalFlip(), ToTensor(),
+                    Normalize(IMAGENET_MEAN, IMAGENET_STD)])
 
 
 def affine_train_transform():

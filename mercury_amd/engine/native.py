@@ -33,7 +33,7 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
-from ..data.augment import SPEC_PARAMS, SpecRecipe
+from ..data.augment import PHOTO_PARAMS, SPEC_PARAMS, SpecRecipe
 from ..ops import hconv, tune
 from ..ops.conv import cpad8, slab_bytes
 from ..parallel.buckets import default_bucket_bytes
@@ -159,7 +159,7 @@ class NativeEngine(object):
         if isinstance(self.eval_augment, SpecRecipe):
             raise ValueError('eval_augment: a SpecRecipe augments training pools only')
         self.aug_params = None           # [P][8] fp32: the last pool's draws (set_shard);
-        #                                  [P][12] for a SpecRecipe
+        #                                  [P][12] for a SpecRecipe, [P][16] with rrc / jitter
         self.seed = seed
         self.alpha, self.ema_alpha, self.importance = alpha, ema_alpha, importance
         self.world_size = world_size
@@ -859,7 +859,8 @@ class NativeEngine(object):
         if x.shape[0] < 1:
             raise ValueError('empty shard')
         if self.augment is not None and self.aug_params is None:
-            n = SPEC_PARAMS if isinstance(self.augment, SpecRecipe) else 8
+            n = SPEC_PARAMS if isinstance(self.augment, SpecRecipe) else \
+                PHOTO_PARAMS if self.augment.photo else 8
             self.aug_params = torch.zeros(self.P, n, dtype=torch.float32, device=self.device)
         # (a shard smaller than one batch -- possible for a Dirichlet non-IID split at large
         # world size -- is cycled: every batch is the shard's epoch permutation, wrapped)
@@ -1548,7 +1549,8 @@ def _image_hw(x):
 def _config_recipes(cfg, presam_loader, test_loader):
     """``Config.augment`` -> (train recipe, eval recipe): 'cifar' keeps the engine's built-in
     pipeline (None, None); 'dataset' reads the loaders' ``dataset.transform``; anything else
-    is an ``AugmentRecipe.parse`` spec, evaluated with its Resize, crop and Normalize only.
+    is an ``AugmentRecipe.parse`` spec, evaluated with its Resize, crop (``rrc`` included: there
+    is no CenterCrop) and Normalize only.
     A spec starting with ``spec:`` (``SpecRecipe.parse``), or a ``transforms.SpecAugment`` as
     the train dataset's transform, gives that spectrogram recipe and no eval recipe."""
     from ..data.augment import AugmentRecipe
@@ -1565,7 +1567,8 @@ def _config_recipes(cfg, presam_loader, test_loader):
             return tr[0].recipe, None
         return AugmentRecipe.from_transform(tr[0]), AugmentRecipe.from_transform(tr[1])
     aug = AugmentRecipe.parse(spec)
-    return aug, dataclasses.replace(aug, flip=False, degrees=0.0, scale=None, cutout=0)
+    return aug, dataclasses.replace(aug, flip=False, degrees=0.0, scale=None, cutout=0,
+                                    jitter=None)
 
 
 class NativeTrainer(Trainer):
