@@ -4,9 +4,12 @@ modes) and backward at the presets' head shapes.  The head path is read once per
 setting.
 
     MERCURY_HEAD_PATH=2 python bench/head_bench.py
+    python bench/head_bench.py --smooth 0.1 --topk 5     # the train shapes with label smoothing
+                                                         # and the top-k count (score shapes: as ever)
 """
 from __future__ import annotations
 
+import argparse
 import json
 import os
 import sys
@@ -23,6 +26,10 @@ SHAPES = [('mobilenetv2', 320, 16, 1280, 100), ('mobilenetv2', 32, 16, 1280, 100
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--smooth', type=float, default=0.0)
+    ap.add_argument('--topk', type=int, default=0)
+    args = ap.parse_args()
     import torch
     from mercury_amd import ops
     ops.lib()
@@ -43,13 +50,18 @@ def main():
         dact = torch.empty(B * HW * C, device=dev, dtype=torch.bfloat16)
         mode = 'score' if B in (320, 1280) else 'train'
 
+        # (score mode takes neither: smoothing is the training loss's, score touches no meter)
+        extra = dict(smooth=args.smooth, topk=args.topk) if mode == 'train' else {}
+
         def fwd():
             ops.head_fwd(act, w, b, label, B, HW, C, K, mode, pooled=pooled, logits=logits,
                          dlogits=dlogits if mode == 'train' else None, losses=losses,
-                         isw=isw if mode == 'train' else None, meters=meters)
+                         isw=isw if mode == 'train' else None, meters=meters, **extra)
         t_f = gtime(fwd, reps=8)
         rec = dict(net=name, B=B, HW=HW, C=C, classes=K, mode=mode, fwd_us=round(t_f, 1),
                    path=os.environ.get('MERCURY_HEAD_PATH', '0'))
+        if args.smooth or args.topk:
+            rec.update(smooth=args.smooth, topk=args.topk)
         if mode == 'train':
             t_b = gtime(lambda: ops.head_bwd(pooled, dlogits, w, dw, db, dact, B, HW, C, K),
                         reps=8)

@@ -470,12 +470,13 @@ PYBIND11_MODULE(_C, m) {
     check_launch("bn_running");
   });
 
-  m.def("head_fwd", [](uintptr_t act, uintptr_t w, uintptr_t b, uintptr_t label, uintptr_t isw,
+  auto head_fwd = [](uintptr_t act, uintptr_t w, uintptr_t b, uintptr_t label, uintptr_t isw,
                        uintptr_t pooled, uintptr_t logits, uintptr_t dlogits, uintptr_t losses,
                        uintptr_t meters, int B, int HW, int C, int classes, int mode, uintptr_t st,
                        int score_kind, uintptr_t bn_res, uintptr_t bn_stats, uintptr_t bn_rmean,
                        uintptr_t bn_rvar, uintptr_t bn_gamma, uintptr_t bn_beta,
-                       float bn_inv_count, float bn_eps, int bn_group_imgs, int bn_act) {
+                       float bn_inv_count, float bn_eps, int bn_group_imgs, int bn_act,
+                       float smooth, int topk) {
     HeadArgs a{P<const bf16>(act), P<const float>(w), P<const float>(b), P<const int>(label),
                P<const float>(isw), P<float>(pooled), P<float>(logits), P<float>(dlogits),
                P<float>(losses), P<float>(meters), B, HW, C, classes, mode, 0, score_kind, 0};
@@ -493,23 +494,51 @@ PYBIND11_MODULE(_C, m) {
       a.bn_group_imgs = bn_group_imgs;
       a.bn_act = bn_act;
     }
+    a.smooth = smooth;
+    a.topk = topk;
     head_fwd_launch(a, S(st));
     check_launch("head_fwd");
+  };
+  // the 27-argument form and the same with (smooth, topk) behind it
+  m.def("head_fwd", [head_fwd](uintptr_t act, uintptr_t w, uintptr_t b, uintptr_t label,
+                               uintptr_t isw, uintptr_t pooled, uintptr_t logits,
+                               uintptr_t dlogits, uintptr_t losses, uintptr_t meters, int B, int HW,
+                               int C, int classes, int mode, uintptr_t st, int score_kind,
+                               uintptr_t bn_res, uintptr_t bn_stats, uintptr_t bn_rmean,
+                               uintptr_t bn_rvar, uintptr_t bn_gamma, uintptr_t bn_beta,
+                               float bn_inv_count, float bn_eps, int bn_group_imgs, int bn_act) {
+    head_fwd(act, w, b, label, isw, pooled, logits, dlogits, losses, meters, B, HW, C, classes,
+             mode, st, score_kind, bn_res, bn_stats, bn_rmean, bn_rvar, bn_gamma, bn_beta,
+             bn_inv_count, bn_eps, bn_group_imgs, bn_act, 0.f, 0);
   });
+  m.def("head_fwd", head_fwd);
   // speech-VGG head (flatten -> fc1 -> fc2 -> log-softmax CE), head.hip
-  m.def("mlp_head_fwd", [](uintptr_t x, uintptr_t w1, uintptr_t b1, uintptr_t w2, uintptr_t b2,
+  auto mlp_head_fwd = [](uintptr_t x, uintptr_t w1, uintptr_t b1, uintptr_t w2, uintptr_t b2,
                            uintptr_t h1, uintptr_t logits, uintptr_t label, uintptr_t isw,
                            uintptr_t dlogits, uintptr_t losses, uintptr_t meters, int B, int F,
-                           int H1, int K, int mode, int score_kind, int splits, uintptr_t st) {
-    mlp_head_fwd_launch(P<const bf16>(x), P<const bf16>(w1), P<const float>(b1),
-                        P<const float>(w2), P<const float>(b2), P<float>(h1), P<float>(logits), B,
-                        F, H1, K, splits, S(st));
+                           int H1, int K, int mode, int score_kind, int splits, uintptr_t st,
+                           float smooth, int topk) {
     HeadArgs a{nullptr, P<const float>(w2), P<const float>(b2), P<const int>(label),
                P<const float>(isw), P<float>(h1), P<float>(logits), P<float>(dlogits),
                P<float>(losses), P<float>(meters), B, 1, H1, K, mode, 0, score_kind, 1};
+    a.smooth = smooth;
+    a.topk = topk;
+    head_check_extras(a, "mlp_head_fwd");      // before the two GEMMs write h1 / logits
+    mlp_head_fwd_launch(P<const bf16>(x), P<const bf16>(w1), P<const float>(b1),
+                        P<const float>(w2), P<const float>(b2), P<float>(h1), P<float>(logits), B,
+                        F, H1, K, splits, S(st));
     head_loss_launch(a, S(st));
     check_launch("mlp_head_fwd");
+  };
+  m.def("mlp_head_fwd", [mlp_head_fwd](uintptr_t x, uintptr_t w1, uintptr_t b1, uintptr_t w2,
+                                       uintptr_t b2, uintptr_t h1, uintptr_t logits,
+                                       uintptr_t label, uintptr_t isw, uintptr_t dlogits,
+                                       uintptr_t losses, uintptr_t meters, int B, int F, int H1,
+                                       int K, int mode, int score_kind, int splits, uintptr_t st) {
+    mlp_head_fwd(x, w1, b1, w2, b2, h1, logits, label, isw, dlogits, losses, meters, B, F, H1, K,
+                 mode, score_kind, splits, st, 0.f, 0);
   });
+  m.def("mlp_head_fwd", mlp_head_fwd);
   m.def("mlp_head_bwd", [](uintptr_t dlogits, uintptr_t h1, uintptr_t x, uintptr_t w1, uintptr_t w2,
                            uintptr_t dh1, uintptr_t dw1, uintptr_t db1, uintptr_t dw2, uintptr_t db2,
                            uintptr_t dx, int B, int F, int H1, int K, uintptr_t st) {

@@ -6,11 +6,15 @@
 // mean_i(l_i / w_i) (`:133-145`) and its gradient
 // dz_i = (softmax(z_i) - onehot(y_i)) / (B * w_i), written in the same launch,
 // plus device-side meters (loss sum, sample count, correct count) so the hot
-// loop never syncs for `.item()` (`util.py:226-231`).
+// loop never syncs for `.item()` (`util.py:226-231`).  Train mode optionally smooths the
+// labels (HeadArgs::smooth: dz and the loss meter only, losses[] stays plain CE); train and
+// eval mode optionally count top-k hits by the rank of the label's logit (HeadArgs::topk).
 //
 // One workgroup per sample: the pooled feature vector and the logits stay in
 // LDS; dot products are wave64 reductions.
 #include <cstdlib>
+#include <stdexcept>
+#include <string>
 
 #include "bn_math.h"
 #include "kernels.h"
@@ -335,27 +339,56 @@ __global__ __launch_bounds__(NT) void head_fwd_kernel(HeadArgs a) {
       for (int c = lane; c < a.C; c += 64) h2 += pooled[c] * pooled[c];
       score = sqrtf(wave_sum(g2) * (wave_sum(h2) + 1.f));
     }
+    // label smoothing s (train only; the launchers refuse it elsewhere): the training loss is
+    // F.cross_entropy(label_smoothing=s) = (1 - s) (lse - z[y]) + s (lse - mean_k z[k]); the
+    // losses[] output and the score stay plain.  Uniform per launch.
+    const float smooth = a.mode == 1 ? a.smooth : 0.f;
+    float tloss = loss;
+    if (smooth != 0.f) {
+      float zs = 0.f;
+      for (int k = lane; k < a.classes; k += 64) zs += logit[k];
+      zs = wave_sum(zs);
+      tloss = (1.f - smooth) * loss + smooth * (lse - zs / (float)a.classes);
+    }
+    // top-k by the rank of the label's logit: the classes above it plus the equal ones before
+    // it (the argmax's tie rule, so rank 0 is am == y); a NaN label logit is no hit.  Uniform
+    // per launch.
+    float hitk = 0.f;
+    if (a.topk > 0 && (a.mode == 1 || a.mode == 2)) {
+      const float zy = logit[y];
+      float above = 0.f;
+      for (int k = lane; k < a.classes; k += 64) {
+        const float z = logit[k];
+        above += (z > zy || (z == zy && k < y)) ? 1.f : 0.f;
+      }
+      above = wave_sum(above);                  // (a count <= classes: exact in fp32)
+      hitk = (zy == zy && above < (float)a.topk) ? 1.f : 0.f;
+    }
     if (lane == 0) {
       if (a.losses) a.losses[b] = score;
       red[0] = lse;
       const float wi = a.isw ? a.isw[b] : 1.f;
       if (a.mode == 1 || a.mode == 2) {
         if (a.meters) {
-          atomicAdd(&a.meters[0], a.mode == 1 ? loss / wi : loss);
+          atomicAdd(&a.meters[0], a.mode == 1 ? tloss / wi : loss);
           atomicAdd(&a.meters[1], 1.f);
           atomicAdd(&a.meters[2], am == y ? 1.f : 0.f);
+          if (a.topk > 0) atomicAdd(&a.meters[5], hitk);
         }
       }
       red[1] = 1.f / ((float)a.B * wi);
+      red[2] = smooth;
     }
   }
   __syncthreads();
   if (a.mode == 1 && a.dlogits) {
-    const float lse = red[0], scale = red[1];
+    // dz = softmax - (1 - s) onehot - s / K; with s = 0 the target is 1 or 0 exactly as before
+    const float lse = red[0], scale = red[1], smooth = red[2];
+    const float hot = 1.f - smooth, rest = smooth / (float)a.classes;
     const int y = a.label[b];
     for (int k = tid; k < a.classes; k += NT) {
       const float p = __expf(logit[k] - lse);
-      a.dlogits[(size_t)b * a.classes + k] = (p - (k == y ? 1.f : 0.f)) * scale;
+      a.dlogits[(size_t)b * a.classes + k] = (p - ((k == y ? hot : 0.f) + rest)) * scale;
     }
   }
 }
@@ -473,7 +506,21 @@ __global__ __launch_bounds__(NT) void head_bwd_kernel(HeadBwdArgs a) {
 }
 }  // namespace
 
+// label smoothing is the training loss's alone, and top-k counts into a meter: a launch that
+// could not honour either is refused before anything is enqueued (never a silent no-op)
+void head_check_extras(const HeadArgs& a, const char* who) {
+  if (!(a.smooth >= 0.f && a.smooth < 1.f))       // (a NaN fails too)
+    throw std::invalid_argument(std::string(who) + ": label smoothing must be in [0, 1)");
+  if (a.smooth != 0.f && a.mode != 1)
+    throw std::invalid_argument(std::string(who) +
+                                ": label smoothing applies to train mode only (score and eval "
+                                "stay plain cross-entropy)");
+  if (a.topk < 0 || a.topk > a.classes)
+    throw std::invalid_argument(std::string(who) + ": topk must be in [0, classes]");
+}
+
 void head_fwd_launch(const HeadArgs& a0, hipStream_t st) {
+  head_check_extras(a0, "head_fwd");
   HeadArgs a = a0;
   a.logits_ready = 0;
   static const int path = [] {
@@ -551,6 +598,7 @@ void mlp_head_bwd_launch(const float* dlogits, const float* h1, const bf16* x, c
 // loss / dlogits / meters / score from precomputed logits (a.pooled: the classifier input, for
 // the gradient-norm score)
 void head_loss_launch(const HeadArgs& a0, hipStream_t st) {
+  head_check_extras(a0, "head_loss");
   HeadArgs a = a0;
   a.logits_ready = 1;
   const size_t shm = (size_t)(a.C + a.classes + 16) * sizeof(float);

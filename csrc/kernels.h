@@ -95,7 +95,16 @@ struct HeadArgs {
   int bn_group_imgs = 1;
   int bn_act = 0;                // 0 none, 1 relu, 2 relu6
   int pooled_ready = 0;          // (set by head_fwd_launch) pooled[] already written
+  // train mode only: F.cross_entropy's label_smoothing in [0, 1) -- dlogits and meters[0] are the
+  // smoothed loss's; losses[] (and score / eval mode as a whole) stay plain CE
+  float smooth = 0.f;
+  // train / eval: k >= 1 adds the samples whose label ranks below k (lower index wins a tie, so
+  // k = 1 is the argmax count) to meters[5]; 0 = off
+  int topk = 0;
 };
+// throws std::invalid_argument: smooth outside [0, 1) or non-zero outside train mode, topk
+// outside [0, classes] (the launchers call it before they enqueue anything)
+void head_check_extras(const HeadArgs& a, const char* who);
 void head_fwd_launch(const HeadArgs& a, hipStream_t st);
 void head_loss_launch(const HeadArgs& a, hipStream_t st);
 

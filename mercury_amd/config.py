@@ -52,6 +52,9 @@ class Config:
     weight_decay: float = 0.0
     clip_grad_norm: float = 0.0     # clip the gradient's global L2 norm to this before the optimizer
                                     # step (torch.nn.utils.clip_grad_norm_); 0 = off
+    label_smoothing: float = 0.0    # F.cross_entropy's label_smoothing, in [0, 1): the training loss
+                                    # and its gradient only -- scoring and evaluation stay plain CE
+    topk: int = 0                   # 0 = off; k >= 2 reports top-k accuracy beside top-1
     num_epochs: int = 100
     max_samples: int = 10_000_000   # `fit` stops once step*W exceeds this
     seed: int = 102

@@ -135,8 +135,15 @@ class NativeEngine(object):
                  sampler='alias', exchange_scores=False, global_table=True, score='loss',
                  global_ema=False, autotune=None, force_buckets=False, comm='auto',
                  wire_bf16=False, debug=False, check_order=False, grad_compress=None,
-                 opts=None, augment=None, eval_augment=None, clip_grad_norm=0.0):
+                 opts=None, augment=None, eval_augment=None, clip_grad_norm=0.0,
+                 label_smoothing=0.0, topk=0):
         self.clip_grad_norm = ops.optim.check_max_norm(clip_grad_norm)
+        from ..utils.meters import check_label_smoothing, check_topk
+        # the train head's label smoothing (scoring and evaluation stay plain CE) and the k of
+        # the top-k hit count of the train and eval heads (meters[5]; 0 = off)
+        self.label_smoothing = check_label_smoothing(label_smoothing)
+        self.topk = check_topk(topk)
+        self.eval_topk = (0, 0)          # (top-k hits, count) of the last evaluate_arrays call
         ops.lib()
         _warn_hw_queues()
         from ..config import EngineOptions
@@ -150,6 +157,7 @@ class NativeEngine(object):
         self.P = batch_size * pool_batches
         self.pool_batches = pool_batches
         self.classes = self.lw.num_classes
+        check_topk(self.topk, self.classes)
         self.H, self.W = image_hw
         # augmentation recipes (data/augment.py) of the pool builds and of evaluate_arrays;
         # None: RandomCrop(pad 4) + flip + CIFAR Normalize on a shard of the input size, and
@@ -639,7 +647,9 @@ class NativeEngine(object):
                          self.lw.fc1.out_features, self.classes, mode, isw=isw,
                          dlogits=m.dlogits if mode == 'train' else None, losses=m.losses,
                          meters=meters if mode != 'score' else None,
-                         score=self.score if mode == 'score' else 'loss')
+                         score=self.score if mode == 'score' else 'loss',
+                         smooth=self.label_smoothing if mode == 'train' else 0.0,
+                         topk=self.topk if mode != 'score' else 0)
 
     def _mlp_head_bwd(self, m, dout):
         """Grads of fc2 / fc1 into the flat buffer and d(activation) (NHWC bf16) into dout."""
@@ -659,7 +669,9 @@ class NativeEngine(object):
                      logits=m.logits,
                      dlogits=getattr(m, 'dlogits', None) if mode == 'train' else None,
                      losses=m.losses, isw=isw, meters=meters,
-                     score=self.score if mode == 'score' else 'loss', bn=hb)
+                     score=self.score if mode == 'score' else 'loss', bn=hb,
+                     smooth=self.label_smoothing if mode == 'train' else 0.0,
+                     topk=self.topk if mode != 'score' else 0)
 
     def flush_dw_reduces(self, m):
         """The deferred depthwise wgrad reduces of this backward, in one launch."""
@@ -1509,7 +1521,8 @@ class NativeEngine(object):
             if recipe is not None:
                 loss_sum += m.losses[:b].double().sum()
             done += b
-        r = self.eval_meters[:3].tolist()
+        r = self.eval_meters[:6].tolist()
+        self.eval_topk = (int(r[5]), int(r[1]))
         if recipe is not None:
             r[0] = loss_sum.item()
         return r[0] / max(r[1], 1), r[2] / max(r[1], 1), int(r[1])
@@ -1526,7 +1539,8 @@ class NativeEngine(object):
             # host-synchronised already: a device barrier that gave up on a peer (its error word)
             # fails loudly here instead of turning into silent replica divergence
             self.xgmi.check()
-        return {'loss_sum': b[0], 'count': b[1], 'correct': b[2], 'pool_mean': b[3], 'ema': b[4]}
+        return {'loss_sum': b[0], 'count': b[1], 'correct': b[2], 'pool_mean': b[3], 'ema': b[4],
+                'correct_k': b[5]}
 
 
 # ---------------------------------------------------------------------- trainer
@@ -1620,7 +1634,9 @@ class NativeTrainer(Trainer):
             score=cfg.score, global_ema=cfg.global_ema, wire_bf16=cfg.wire_bf16,
             grad_compress=cfg.grad_compress,
             comm=cfg.comm, debug=cfg.debug, check_order=cfg.check_order,
-            force_buckets=cfg.force_buckets, clip_grad_norm=cfg.clip_grad_norm)
+            force_buckets=cfg.force_buckets, clip_grad_norm=cfg.clip_grad_norm,
+            label_smoothing=cfg.label_smoothing, topk=cfg.topk)
+        self.label_smoothing, self.topk = self.engine.label_smoothing, self.engine.topk
         self.engine.set_shard(x, y)
         self.engine.roctx = cfg.roctx
         from ..utils.profiling import StepWindow
@@ -1667,9 +1683,10 @@ class NativeTrainer(Trainer):
         e = self.engine
         running_train_loss = Average()
         presam_ema_loss = EMAverage(self.cfg.ema_alpha)
-        runing_train_acc = Accuracy()
+        runing_train_acc = Accuracy(self._report_k())
         e.reset_ema()                      # reference: fresh EMAverage per epoch (`:121`)
         e.meters[:3].zero_()
+        e.meters[5:6].zero_()
         self._sync_lr()
         e.prime()
         t0 = time.perf_counter()
@@ -1696,7 +1713,7 @@ class NativeTrainer(Trainer):
                 break
         m = e.read_meters()
         running_train_loss.update(m['loss_sum'] / max(m['count'], 1), max(int(m['count']), 1))
-        runing_train_acc.update_counts(m['correct'], int(m['count']))
+        runing_train_acc.update_counts(m['correct'], int(m['count']), m['correct_k'])
         presam_ema_loss.update(m['ema'])
         return running_train_loss, runing_train_acc, presam_ema_loss
 
@@ -1720,9 +1737,11 @@ class NativeTrainer(Trainer):
             # the last step's norm (before clipping); read here only -- it is a host sync
             gn = self.engine.opt.last_grad_norm()
             clip = ', grad_norm: {:.6g}'.format(gn)
-        print('step:{}, running train loss: {:.6f}, running train acc: {:.2f}%, '
+        k = self._report_k()
+        topk = ', top{}: {:.2f}%'.format(k, 100 * m['correct_k'] / cnt) if k else ''
+        print('step:{}, running train loss: {:.6f}, running train acc: {:.2f}%{}, '
               'presam_ema_loss: {:.6f}, pool_mean: {:.4f}{}, {:.3f} ms/step{}'.format(
-                  self.step, m['loss_sum'] / cnt, 100 * m['correct'] / cnt, m['ema'],
+                  self.step, m['loss_sum'] / cnt, 100 * m['correct'] / cnt, topk, m['ema'],
                   m['pool_mean'], clip,
                   (time.perf_counter() - t0) * 1e3 / self.cfg.print_every, dev),
               flush=True)
@@ -1738,17 +1757,17 @@ class NativeTrainer(Trainer):
             self.writer.add_scalar('test/acc', test_acc.accuracy, self.step)
             self.writer.add_scalar('train/loss', train_loss.average, self.step)
             self.writer.add_scalar('test/loss', test_loss.average, self.step)
+            self._write_acc_k(train_acc, test_acc)
             if self.engine.opt.clip_on:
                 self.writer.add_scalar('train/grad_norm', self.engine.opt.last_grad_norm(),
                                        self.step)
         if self.rank == 0:
-            print('(Eval) Step: {}, train loss: {}, train acc: {} test loss: {}, test acc: {}'
-                  .format(self.step, train_loss, train_acc, test_loss, test_acc), flush=True)
+            self._print_eval(train_loss, train_acc, test_loss, test_acc)
 
     def evaluate(self, max_batches=None):
         out = []
         for loader in (self.train_loader, self.test_loader):
-            lm, am = Average(), Accuracy()
+            lm, am = Average(), Accuracy(self._report_k())
             if loader is not None:
                 x, y = _dataset_arrays(loader)
                 bs = getattr(loader, 'batch_size', 32) or 32
@@ -1757,7 +1776,7 @@ class NativeTrainer(Trainer):
                     n = min(n, max_batches * bs)
                 loss, acc, cnt = self.engine.evaluate_arrays(x[:n], y[:n])
                 lm.update(loss, cnt)
-                am.update_counts(acc * cnt, cnt)
+                am.update_counts(acc * cnt, cnt, self.engine.eval_topk[0])
             out += [lm, am]
         return out[0], out[1], out[2], out[3]
 

@@ -37,7 +37,7 @@ from .importance import pool as ispool
 from .parallel.buckets import BucketedAllReduce
 from .parallel.flat import FlatParams
 from .utils.logging import MetricsWriter, PhaseTimer
-from .utils.meters import Accuracy, Average, EMAverage
+from .utils.meters import (Accuracy, Average, EMAverage, check_label_smoothing, check_topk)
 
 
 class Trainer(object):
@@ -69,6 +69,7 @@ class Trainer(object):
         self.bucketer = None
         self._setup_flat()
         self._setup_clip()
+        self._setup_loss_head()
         self._fc_in = None
         if self.cfg.score == 'gradnorm':
             fcs = [m for m in net.modules() if isinstance(m, torch.nn.Linear)]
@@ -90,6 +91,16 @@ class Trainer(object):
         if self.cfg.score == 'gradnorm':
             return ispool.classifier_gradnorm(output, label, self._fc_in)
         return F.cross_entropy(output.float(), label, reduction='none')
+
+    def _setup_loss_head(self):
+        """``cfg.label_smoothing`` (the training loss only) and ``cfg.topk`` (top-k accuracy
+        beside top-1 from k = 2 on), validated."""
+        self.label_smoothing = check_label_smoothing(self.cfg.label_smoothing)
+        self.topk = check_topk(self.cfg.topk, getattr(self.cfg, 'num_classes', None))
+
+    def _report_k(self):
+        """k when top-k accuracy is reported (cfg.topk >= 2), else 0."""
+        return self.topk if self.topk >= 2 else 0
 
     # ------------------------------------------------------------------ DP plumbing
     def _setup_flat(self):
@@ -226,7 +237,8 @@ class Trainer(object):
     def train_step(self, probs, i_data, i_label, ema, running_loss, running_acc):
         t = self.timer.start('fwd_bwd')
         output = self.net(i_data)
-        losses = F.cross_entropy(output.float(), i_label, reduction='none')
+        losses = F.cross_entropy(output.float(), i_label, reduction='none',
+                                 label_smoothing=self.label_smoothing)
         running_acc.update(output, i_label)
         loss = ispool.weighted_loss(losses, probs)
         self.flat.zero_grad()
@@ -249,7 +261,7 @@ class Trainer(object):
     def train(self):
         running_train_loss = Average()
         presam_ema_loss = EMAverage(self.cfg.ema_alpha)
-        runing_train_acc = Accuracy()
+        runing_train_acc = Accuracy(self._report_k())
         probs, i_data, i_label, _, _ = self.update_samples(presam_ema_loss)
         for _ in range(max(0, self.steps_per_epoch - self.epoch_step)):
             t0 = time.perf_counter()
@@ -304,9 +316,10 @@ class Trainer(object):
         self._health()
         if cfg.print_every and self.step % cfg.print_every == 0 and self.rank == 0:
             ph = self.timer.collect()
-            print('step:{}, running train loss: {}, running train acc: {}, presam_ema_loss: {}, '
+            print('step:{}, running train loss: {}, running train acc: {}{}, presam_ema_loss: {}, '
                   'step time:{:.3f}, {}'.format(
-                      self.step, running_loss, running_acc, ema, time.perf_counter() - t0,
+                      self.step, running_loss, running_acc, self._acc_k_str(running_acc), ema,
+                      time.perf_counter() - t0,
                       ', '.join('{}:{:.3f}ms'.format(k, v) for k, v in ph.items())) + (
                           '' if self._grad_norm is None else
                           ', grad_norm: {:.6g}'.format(float(self._grad_norm))), flush=True)
@@ -318,11 +331,27 @@ class Trainer(object):
                 self.writer.add_scalar('test/acc', test_acc.accuracy, self.step)
                 self.writer.add_scalar('train/loss', train_loss.average, self.step)
                 self.writer.add_scalar('test/loss', test_loss.average, self.step)
+                self._write_acc_k(train_acc, test_acc)
                 if self._grad_norm is not None:
                     self.writer.add_scalar('train/grad_norm', float(self._grad_norm), self.step)
             if self.rank == 0:
-                print('(Eval) Step: {}, train loss: {}, train acc: {} test loss: {}, test acc: {}'
-                      .format(self.step, train_loss, train_acc, test_loss, test_acc), flush=True)
+                self._print_eval(train_loss, train_acc, test_loss, test_acc)
+
+    def _acc_k_str(self, acc):
+        """', top5: 93.10%' behind a printed top-1 accuracy when top-k is reported, else ''."""
+        k = self._report_k()
+        return ', top{}: {:.2f}%'.format(k, acc.accuracy_k * 100) if k else ''
+
+    def _write_acc_k(self, train_acc, test_acc):
+        k = self._report_k()
+        if k and self.writer is not None:
+            self.writer.add_scalar('train/acc_top%d' % k, train_acc.accuracy_k, self.step)
+            self.writer.add_scalar('test/acc_top%d' % k, test_acc.accuracy_k, self.step)
+
+    def _print_eval(self, train_loss, train_acc, test_loss, test_acc):
+        print('(Eval) Step: {}, train loss: {}, train acc: {}{} test loss: {}, test acc: {}{}'
+              .format(self.step, train_loss, train_acc, self._acc_k_str(train_acc), test_loss,
+                      test_acc, self._acc_k_str(test_acc)), flush=True)
 
     def fit(self, epochs):
         if self.rank == 0:
@@ -362,8 +391,9 @@ class Trainer(object):
             self.writer.close()
 
     def evaluate(self, max_batches=None):
-        test_loss, test_acc = Average(), Accuracy()
-        train_loss, train_acc = Average(), Accuracy()
+        k = self._report_k()
+        test_loss, test_acc = Average(), Accuracy(k)
+        train_loss, train_acc = Average(), Accuracy(k)
         self.net.eval()
         with torch.no_grad():
             for loader, lm, am in ((self.train_loader, train_loss, train_acc),
