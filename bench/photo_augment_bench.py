@@ -1,13 +1,14 @@
-"""Cost of the photographic recipes (csrc/photo.hip pool_photo_kernel).
+"""Cost of the image recipes (csrc/pool_recipe.hip pool_recipe_kernel).
 
     python bench/photo_augment_bench.py pool [--out FILE] [--runs R]
     python bench/photo_augment_bench.py step [--out FILE] [--steps K] [--warmup W] [--runs R]
 
 ``pool``: ``bench/gtime.py`` time of one pool build at P = 320, 32x32 from a 40x40 shard, and at
-P = 1280, 224x224 from a 256x256 shard (batch 32 and 128): ``pool_augment_kernel``'s crop + flip
-recipe as the yardstick against ``pool_photo_kernel`` with rrc + flip, rrc + flip + jitter
-without contrast (one sweep) and rrc + flip + full jitter (two sweeps).  Every call advances the
-pool counter, so successive builds read other samples.  The variants are interleaved,
+P = 1280, 224x224 from a 256x256 shard (batch 32 and 128): the crop + flip recipe as the
+yardstick against rrc + flip, rrc + flip + jitter without contrast (one sweep) and rrc + flip +
+full jitter (two sweeps); at P = 320 also Resize(33) + RandomCrop(32) and the whole
+``load_cifar10`` recipe (resize, crop, flip, affine) from a 32x32 shard.  Every call advances
+the pool counter, so successive builds read other samples.  The variants are interleaved,
 ``--runs`` times.
 
 ``step``: the resnet50-imagenet preset built as ``bench.py`` builds it, ms/step with
@@ -61,16 +62,21 @@ def bench_pool(args):
         pl = torch.zeros(P, dtype=torch.int32, device=dev)
         pi = torch.zeros(P, dtype=torch.int32, device=dev)
         kw = dict(crop=(hw, hw), flip=True, mean=MEAN, std=STD)
-        recipes = [('pool_augment_kernel crop + flip', AugmentRecipe(**kw)),
-                   ('pool_photo_kernel rrc + flip', AugmentRecipe(rrc=RRC, **kw)),
-                   ('pool_photo_kernel rrc + flip + jitter without contrast',
-                    AugmentRecipe(rrc=RRC, jitter=NO_CONTRAST, **kw)),
-                   ('pool_photo_kernel rrc + flip + full jitter',
-                    AugmentRecipe(rrc=RRC, jitter=FULL, **kw))]
+        recipes = [('crop + flip', AugmentRecipe(**kw), shard),
+                   ('rrc + flip', AugmentRecipe(rrc=RRC, **kw), shard),
+                   ('rrc + flip + jitter without contrast',
+                    AugmentRecipe(rrc=RRC, jitter=NO_CONTRAST, **kw), shard),
+                   ('rrc + flip + full jitter', AugmentRecipe(rrc=RRC, jitter=FULL, **kw), shard)]
+        if hw == 32:                    # the IID loaders' test and train pipelines, 32x32 source
+            small = shard[:, :32, :32].contiguous()
+            recipes += [('resize 33 + crop', AugmentRecipe(resize=33, crop=(32, 32)), small),
+                        ('resize 35 + crop + flip + affine',
+                         AugmentRecipe(resize=35, crop=(32, 32), flip=True, degrees=10.0,
+                                       scale=(0.9, 1.1)), small)]
 
-        def build(recipe):
+        def build(recipe, src_shard):
             def fn():
-                ops.pool_build(shard, labels, ctrl, pool, pl, pi, P, B, 7, recipe=recipe,
+                ops.pool_build(src_shard, labels, ctrl, pool, pl, pi, P, B, 7, recipe=recipe,
                                force_augment_kernel=not recipe.photo)
                 ctrl[0:1].add_(1)
             return fn
@@ -78,13 +84,14 @@ def bench_pool(args):
         def tick():                     # what every variant pays beside its kernel
             ctrl[0:1].add_(1)
 
-        variants = [('counter increment alone', tick)] + [(n, build(r)) for n, r in recipes]
+        variants = [('counter increment alone', tick, src)] + [
+            ('pool_recipe_kernel ' + n, build(r, s), s.shape[1]) for n, r, s in recipes]
         for run in range(args.runs):
-            for label, fn in variants:
+            for label, fn, source in variants:
                 ctrl.zero_()
                 us = gtime(fn, reps=16)
                 emit({'bench': 'photo_pool', 'run': run, 'P': P, 'batch': B, 'out': hw,
-                      'source': src, 'Ns': Ns, 'variant': label, 'us': round(us, 3),
+                      'source': source, 'Ns': Ns, 'variant': label, 'us': round(us, 3),
                       'write_MB': round(0 if fn is tick else 16 * P * hw * hw / 1e6, 2)}, args.out)
 
 

@@ -68,6 +68,30 @@ static void check_launch(const char* what) {
   if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// The block every pool-build kernel shares, field by field (mean, inv_std: three channels).
+static PoolBuildArgs pool_build_args(uintptr_t shard, uintptr_t labels, uintptr_t ctrl,
+                                     uintptr_t pool, uintptr_t pool_label, uintptr_t pool_index,
+                                     int Ns, int H, int W, int Pn, int batch, int pad, int flip,
+                                     int augment, int shuffle, uint32_t seed,
+                                     const std::vector<float>& mean,
+                                     const std::vector<float>& inv_std, int prebuilt,
+                                     uintptr_t zero, int nzero) {
+  PoolBuildArgs b{};
+  b.shard = P<const uint8_t>(shard);
+  b.labels = P<const int64_t>(labels);
+  b.ctrl = P<const int64_t>(ctrl);
+  b.pool = P<bf16>(pool);
+  b.pool_label = P<int>(pool_label);
+  b.pool_index = P<int>(pool_index);
+  b.Ns = Ns, b.H = H, b.W = W, b.P = Pn, b.batch = batch;
+  b.pad = pad, b.flip = flip, b.augment = augment, b.shuffle = shuffle, b.seed = seed;
+  for (int c = 0; c < 3; ++c) b.mean[c] = mean[c], b.inv_std[c] = inv_std[c];
+  b.prebuilt = prebuilt;
+  b.zero = P<float>(zero);
+  b.nzero = nzero;
+  return b;
+}
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "mercury_amd CDNA4 (gfx950) kernels";
 
@@ -615,41 +639,13 @@ PYBIND11_MODULE(_C, m) {
                          int batch, int pad, int flip, int augment, int shuffle, uint32_t seed,
                          std::vector<float> mean, std::vector<float> inv_std, uintptr_t st,
                          int prebuilt, uintptr_t zero, int nzero) {
-    PoolBuildArgs a{P<const uint8_t>(shard), P<const int64_t>(labels), P<const int64_t>(ctrl),
-                    P<bf16>(pool), P<int>(pool_label), P<int>(pool_index), Ns, H, W, Pn, batch,
-                    pad, flip, augment, shuffle, seed, {mean[0], mean[1], mean[2]},
-                    {inv_std[0], inv_std[1], inv_std[2]}, prebuilt, P<float>(zero), nzero};
-    pool_build_launch(a, S(st));
+    pool_build_launch(pool_build_args(shard, labels, ctrl, pool, pool_label, pool_index, Ns, H, W,
+                                      Pn, batch, pad, flip, augment, shuffle, seed, mean, inv_std,
+                                      prebuilt, zero, nzero), S(st));
     check_launch("pool_build");
   });
-  m.def("pool_augment", [](uintptr_t shard, uintptr_t labels, uintptr_t ctrl, uintptr_t pool,
-                           uintptr_t pool_label, uintptr_t pool_index, int Ns, int Hs, int Ws,
-                           int H, int W, int Pn, int batch, int pad, int flip, int augment,
-                           int shuffle, uint32_t seed, std::vector<float> mean,
-                           std::vector<float> inv_std, uintptr_t st, uintptr_t zero, int nzero,
-                           int resize, int Hr, int Wr, float degrees, float scale_lo,
-                           float scale_hi, int cutout, int affine, uintptr_t params) {
-    if (Ns < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || Pn < 1 || batch < 1 || pad < 0)
-      throw std::runtime_error("pool_augment: sizes must be positive");
-    if (resize ? (Hr < 1 || Wr < 1) : (Hr != Hs || Wr != Ws))
-      throw std::runtime_error("pool_augment: resized size does not match the recipe");
-    if (Hr + 2 * pad < H || Wr + 2 * pad < W)
-      throw std::runtime_error("pool_augment: empty crop range (crop larger than the padded image)");
-    if (degrees < 0.f || !(scale_lo > 0.f) || scale_hi < scale_lo || cutout < 0)
-      throw std::runtime_error("pool_augment: degrees >= 0, 0 < scale_lo <= scale_hi, cutout >= 0");
-    if (mean.size() != 3 || inv_std.size() != 3)
-      throw std::runtime_error("pool_augment: mean and std have three channels");
-    PoolAugmentArgs a{{P<const uint8_t>(shard), P<const int64_t>(labels), P<const int64_t>(ctrl),
-                       P<bf16>(pool), P<int>(pool_label), P<int>(pool_index), Ns, H, W, Pn, batch,
-                       pad, flip, augment, shuffle, seed, {mean[0], mean[1], mean[2]},
-                       {inv_std[0], inv_std[1], inv_std[2]}, 0, P<float>(zero), nzero},
-                      Hs, Ws, resize, Hr, Wr, degrees, scale_lo, scale_hi, cutout, affine,
-                      P<float>(params)};
-    pool_augment_launch(a, S(st));
-    check_launch("pool_augment");
-  });
-  // photographic recipes (photo.hip): keyword arguments only
-  m.def("pool_photo", [](uintptr_t shard, uintptr_t labels, uintptr_t ctrl, uintptr_t pool,
+  // image recipes (pool_recipe.hip): keyword arguments only
+  m.def("pool_recipe", [](uintptr_t shard, uintptr_t labels, uintptr_t ctrl, uintptr_t pool,
                          uintptr_t pool_label, uintptr_t pool_index, uintptr_t params,
                          long long params_floats, uintptr_t zero, int nzero, uintptr_t st, int Ns,
                          int Hs, int Ws, int H, int W, int Pn, int batch, int augment, int shuffle,
@@ -658,60 +654,59 @@ PYBIND11_MODULE(_C, m) {
                          std::vector<float> jitter, int pad, int resize, int Hr, int Wr,
                          float degrees, float scale_lo, float scale_hi, int affine) {
     if (Ns < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || Pn < 1 || batch < 1 || pad < 0)
-      throw std::runtime_error("pool_photo: sizes must be positive");
+      throw std::runtime_error("pool_recipe: sizes must be positive");
     if ((long long)H * W * Pn >= (1LL << 30) || (long long)Hs * Ws >= (1LL << 24))
-      throw std::runtime_error("pool_photo: H*W*P must stay below 2^30 and Hs*Ws below 2^24");
+      throw std::runtime_error("pool_recipe: H*W*P must stay below 2^30 and Hs*Ws below 2^24");
     if (mean.size() != 3 || inv_std.size() != 3)
-      throw std::runtime_error("pool_photo: mean and std have three channels");
+      throw std::runtime_error("pool_recipe: mean and std have three channels");
     if (cutout < 0)
-      throw std::runtime_error("pool_photo: cutout >= 0");
+      throw std::runtime_error("pool_recipe: cutout >= 0");
     if (!(rrc.empty() || rrc.size() == 4) || jitter.size() != 4)
-      throw std::runtime_error("pool_photo: rrc is empty or (scale_lo, scale_hi, ratio_lo, "
+      throw std::runtime_error("pool_recipe: rrc is empty or (scale_lo, scale_hi, ratio_lo, "
                                "ratio_hi), jitter is (brightness, contrast, saturation, hue)");
     for (float v : jitter)
       if (!(v >= 0.f) || !std::isfinite(v))
-        throw std::runtime_error("pool_photo: jitter strengths are finite and >= 0");
+        throw std::runtime_error("pool_recipe: jitter strengths are finite and >= 0");
     if (jitter[3] > 0.5f)
-      throw std::runtime_error("pool_photo: hue must lie in [0, 0.5]");
+      throw std::runtime_error("pool_recipe: hue must lie in [0, 0.5]");
     const bool jit = jitter[0] > 0.f || jitter[1] > 0.f || jitter[2] > 0.f || jitter[3] > 0.f;
-    if (rrc.empty() && !jit)
-      throw std::runtime_error("pool_photo: neither rrc nor jitter is set (pool_augment's case)");
     if (!rrc.empty()) {
       for (float v : rrc)
         if (!std::isfinite(v))
-          throw std::runtime_error("pool_photo: rrc must be finite");
+          throw std::runtime_error("pool_recipe: rrc must be finite");
       if (!(rrc[0] > 0.f) || rrc[1] < rrc[0] || !(rrc[2] > 0.f) || rrc[3] < rrc[2])
-        throw std::runtime_error("pool_photo: rrc needs 0 < scale_lo <= scale_hi and "
+        throw std::runtime_error("pool_recipe: rrc needs 0 < scale_lo <= scale_hi and "
                                  "0 < ratio_lo <= ratio_hi");
       if (pad || resize || affine || degrees != 0.f || Hr != Hs || Wr != Ws)
-        throw std::runtime_error("pool_photo: rrc replaces resize, pad, degrees and scale");
+        throw std::runtime_error("pool_recipe: rrc replaces resize, pad, degrees and scale");
     } else {
       if (resize ? (Hr < 1 || Wr < 1) : (Hr != Hs || Wr != Ws))
-        throw std::runtime_error("pool_photo: resized size does not match the recipe");
+        throw std::runtime_error("pool_recipe: resized size does not match the recipe");
       if (Hr + 2 * pad < H || Wr + 2 * pad < W)
-        throw std::runtime_error("pool_photo: empty crop range (crop larger than the padded image)");
+        throw std::runtime_error("pool_recipe: empty crop range (crop larger than the padded image)");
       if (degrees < 0.f || !(scale_lo > 0.f) || scale_hi < scale_lo)
-        throw std::runtime_error("pool_photo: degrees >= 0, 0 < scale_lo <= scale_hi");
+        throw std::runtime_error("pool_recipe: degrees >= 0, 0 < scale_lo <= scale_hi");
     }
-    if (params && params_floats != (long long)Pn * 16)
-      throw std::runtime_error("pool_photo: params must hold P * 16 floats");
-    PoolPhotoArgs a{{{P<const uint8_t>(shard), P<const int64_t>(labels), P<const int64_t>(ctrl),
-                      P<bf16>(pool), P<int>(pool_label), P<int>(pool_index), Ns, H, W, Pn, batch,
-                      pad, flip, augment, shuffle, seed, {mean[0], mean[1], mean[2]},
-                      {inv_std[0], inv_std[1], inv_std[2]}, 0, P<float>(zero), nzero},
-                     Hs, Ws, resize, Hr, Wr, degrees, scale_lo, scale_hi, cutout, affine, nullptr},
-                    rrc.empty() ? 0 : 1, 1.f, 1.f, 1.f, 1.f, 0.f, 0.f,
-                    {jitter[0], jitter[1], jitter[2], jitter[3]}, P<float>(params)};
+    const int params_ld = !rrc.empty() || jit ? 16 : 8;   // (the launched instantiation's row)
+    if (params && params_floats != (long long)Pn * params_ld)
+      throw std::runtime_error(params_ld == 16 ? "pool_recipe: params must hold P * 16 floats"
+                                               : "pool_recipe: params must hold P * 8 floats");
+    PoolRecipeArgs a{pool_build_args(shard, labels, ctrl, pool, pool_label, pool_index, Ns, H, W,
+                                     Pn, batch, pad, flip, augment, shuffle, seed, mean, inv_std,
+                                     0, zero, nzero),
+                     Hs, Ws, resize, Hr, Wr, degrees, scale_lo, scale_hi, cutout, affine,
+                     rrc.empty() ? 0 : 1, 1.f, 1.f, 1.f, 1.f, 0.f, 0.f,
+                     {jitter[0], jitter[1], jitter[2], jitter[3]}, P<float>(params)};
     if (!rrc.empty()) {
-      a.scale_lo = rrc[0];
-      a.scale_hi = rrc[1];
+      a.area_lo = rrc[0];
+      a.area_hi = rrc[1];
       a.ratio_lo = rrc[2];
       a.ratio_hi = rrc[3];
       a.log_ratio_lo = (float)std::log((double)rrc[2]);
       a.log_ratio_hi = (float)std::log((double)rrc[3]);
     }
-    pool_photo_launch(a, S(st));
-    check_launch("pool_photo");
+    pool_recipe_launch(a, S(st));
+    check_launch("pool_recipe");
   }, py::kw_only(), py::arg("shard"), py::arg("labels"), py::arg("ctrl"), py::arg("pool"),
      py::arg("pool_label"), py::arg("pool_index"), py::arg("params") = 0,
      py::arg("params_floats") = 0, py::arg("zero") = 0, py::arg("nzero") = 0, py::arg("stream"),
@@ -746,10 +741,9 @@ PYBIND11_MODULE(_C, m) {
       throw std::runtime_error("pool_spec: fill must be finite");
     if (chunks < 0)
       throw std::runtime_error("pool_spec: chunks >= 0");
-    PoolSpecArgs a{{P<const uint8_t>(shard), P<const int64_t>(labels), P<const int64_t>(ctrl),
-                    P<bf16>(pool), P<int>(pool_label), P<int>(pool_index), Ns, H, W, Pn, batch,
-                    0, 0, augment, shuffle, seed, {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, 0,
-                    P<float>(zero), nzero},
+    PoolSpecArgs a{pool_build_args(shard, labels, ctrl, pool, pool_label, pool_index, Ns, H, W, Pn,
+                                   batch, 0, 0, augment, shuffle, seed, {0.f, 0.f, 0.f},
+                                   {1.f, 1.f, 1.f}, 0, zero, nzero),
                    C, shift, fmask_n, fmask_max, tmask_n, tmask_max, gain_lo, gain_hi, fill,
                    P<float>(params), chunks};
     pool_spec_launch(a, S(st));

@@ -28,10 +28,7 @@ __global__ __launch_bounds__(256) void pool_take_kernel(PoolBuildArgs a) {
   int64_t gb;
   int t;
   const uint32_t src = pool_src(a, slot, gb, t);
-  if (threadIdx.x == 0) {
-    a.pool_label[slot] = (int)a.labels[src];
-    a.pool_index[slot] = (int)src;
-  }
+  if (threadIdx.x == 0) pool_slot_header(a, slot, src);
   const int npx = a.H * a.W;
   const u32x4* in = (const u32x4*)a.shard + (size_t)src * npx;
   u32x4* out = (u32x4*)a.pool + (size_t)slot * npx;
@@ -46,16 +43,12 @@ __global__ __launch_bounds__(256) void pool_build_kernel(PoolBuildArgs a) {
   const uint32_t src = pool_src(a, slot, gb, t);
   int dy = a.pad, dx = a.pad, flip = 0;
   if (a.augment) {
-    const u32x4 r = philox4x32(u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5eedu},
-                               a.seed, 0xA5A5A5A5u);
+    const u32x4 r = pool_draw(gb, t, DRAW_CROP, a.seed);
     dy = r.x % (2 * a.pad + 1);
     dx = r.y % (2 * a.pad + 1);
     flip = a.flip ? (r.z & 1) : 0;
   }
-  if (threadIdx.x == 0) {
-    a.pool_label[slot] = (int)a.labels[src];
-    a.pool_index[slot] = (int)src;
-  }
+  if (threadIdx.x == 0) pool_slot_header(a, slot, src);
   const uint8_t* img = a.shard + (size_t)src * a.H * a.W * 3;
   bf16* out = a.pool + (size_t)slot * a.H * a.W * 8;
   const int npx = a.H * a.W;
@@ -79,103 +72,6 @@ __global__ __launch_bounds__(256) void pool_build_kernel(PoolBuildArgs a) {
   }
 }
 
-// ---- augmentation recipes (PoolAugmentArgs) ------------------------------------------------
-// (pool_src, zero_slice and the per-tap geometry aug_tap: pool_geom.h, shared with photo.hip)
-// One block per pool slot, like pool_build_kernel, whose crop / flip draw (first Philox call)
-// this repeats word for word: a crop-and-flip recipe on a shard of the output size gives the
-// same bits from either kernel.
-template <bool AFFINE, bool RESIZE>
-__global__ __launch_bounds__(256) void pool_augment_kernel(PoolAugmentArgs a) {
-  const PoolBuildArgs& b = a.b;
-  const int slot = blockIdx.x;
-  if (b.zero) zero_slice(b);
-  int64_t gb;
-  int t;
-  const uint32_t src = pool_src(b, slot, gb, t);
-  const int H = b.H, W = b.W;
-  int dy = (a.Hr + 2 * b.pad - H) / 2, dx = (a.Wr + 2 * b.pad - W) / 2, flip = 0;
-  float angle = 0.f, scale = 1.f;
-  int cut_y = 0, cut_x = 0, cut = 0;
-  if (b.augment) {
-    const u32x4 r = philox4x32(u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5eedu},
-                               b.seed, 0xA5A5A5A5u);
-    dy = r.x % (a.Hr + 2 * b.pad - H + 1);
-    dx = r.y % (a.Wr + 2 * b.pad - W + 1);
-    flip = b.flip ? (r.z & 1) : 0;
-    const u32x4 q = philox4x32(u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5eeeu},
-                               b.seed, 0xA5A5A5A5u);
-    angle = -a.degrees + 2.f * a.degrees * u01(q.x);
-    scale = a.scale_lo + (a.scale_hi - a.scale_lo) * u01(q.y);
-    cut_y = q.z % H;
-    cut_x = q.w % W;
-    cut = a.cutout;
-  }
-  if (threadIdx.x == 0) {
-    b.pool_label[slot] = (int)b.labels[src];
-    b.pool_index[slot] = (int)src;
-    if (a.params) {
-      float* p = a.params + (size_t)slot * 8;
-      p[0] = (float)dy;
-      p[1] = (float)dx;
-      p[2] = (float)flip;
-      p[3] = angle;
-      p[4] = scale;
-      p[5] = (float)cut_y;
-      p[6] = (float)cut_x;
-      p[7] = 0.f;
-    }
-  }
-  // Cutout.__call__: [clip(c - L/2, 0, n), clip(c + L/2, 0, n)) in both axes (empty when off)
-  const int ch = cut / 2;
-  const int cy0 = cut ? max(cut_y - ch, 0) : 0, cy1 = cut ? min(cut_y + ch, H) : 0;
-  const int cx0 = cut ? max(cut_x - ch, 0) : 0, cx1 = cut ? min(cut_x + ch, W) : 0;
-  const float ry = (float)a.Hs / (float)a.Hr, rx = (float)a.Ws / (float)a.Wr;
-  float cs = 1.f, sn = 0.f;
-  if (AFFINE) {
-    const float rad = angle * 0.017453292519943295f;
-    cs = cosf(rad) / scale;
-    sn = sinf(rad) / scale;
-  }
-  const uint8_t* img = b.shard + (size_t)src * a.Hs * a.Ws * 3;
-  bf16* out = b.pool + (size_t)slot * H * W * 8;
-  const int npx = H * W;
-  for (int px = threadIdx.x; px < npx; px += 256) {
-    const int i = px / W, j = px - i * W;
-    float v[3];
-    if (AFFINE) {
-      // affine_grid + grid_sample (bilinear, zeros padding, align_corners=False)
-      const float xn = (2 * j + 1) / (float)W - 1.f, yn = (2 * i + 1) / (float)H - 1.f;
-      const float gx = cs * xn - sn * yn, gy = sn * xn + cs * yn;
-      const float fx = ((gx + 1.f) * W - 1.f) * 0.5f, fy = ((gy + 1.f) * H - 1.f) * 0.5f;
-      const float x0f = floorf(fx), y0f = floorf(fy);   // (floorf: fx, fy can be negative)
-      const float lx = fx - x0f, ly = fy - y0f;
-      const int x0 = (int)x0f, y0 = (int)y0f;
-      v[0] = v[1] = v[2] = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int y = y0 + (k >> 1), x = x0 + (k & 1);
-        if (y < 0 || x < 0 || y >= H || x >= W) continue;
-        const float wt = ((k >> 1) ? ly : 1.f - ly) * ((k & 1) ? lx : 1.f - lx);
-        float tv[3];
-        aug_tap<RESIZE>(a, img, y, x, dy, dx, flip, ry, rx, tv);
-        v[0] += wt * tv[0];
-        v[1] += wt * tv[1];
-        v[2] += wt * tv[2];
-      }
-    } else {
-      aug_tap<RESIZE>(a, img, i, j, dy, dx, flip, ry, rx, v);
-    }
-    const bool hole = i >= cy0 && i < cy1 && j >= cx0 && j < cx1;
-    bf16x8 o;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      o[c] = f2bf(hole ? 0.f : (v[c] * (1.f / 255.f) - b.mean[c]) * b.inv_std[c]);
-#pragma unroll
-    for (int c = 3; c < 8; ++c) o[c] = f2bf(0.f);
-    *(bf16x8*)(out + (size_t)px * 8) = o;
-  }
-}
-
 // ---- spectrogram recipes (PoolSpecArgs) ----------------------------------------------------
 // Planar bf16 shard [Ns][C][H][W] (H frequency rows, W frames) -> NHWC8 pool.  Output pixel
 // (f, t): fill inside a frequency or a time band (bands are in OUTPUT coordinates), else fill
@@ -183,8 +79,7 @@ __global__ __launch_bounds__(256) void pool_augment_kernel(PoolAugmentArgs a) {
 // gain is exactly 1.0f when unset, so values pass through bit for bit.  Channels C..7 are +0.
 //
 // Draws per slot: Philox on the counter (gb, t) of the image kernels, stream words 0x5bec0..2
-// (the image kernels use 0x5eed: dy, dx, flip and 0x5eee: angle, scale, cut_y, cut_x; photo.hip
-// adds 0x5ef0..0x5ef4: box attempts, 0x5ef5: top, left, 0x5ef8: colour factors, 0x5ef9: order):
+// (the image kernels' words and every word's name: pool_geom.h):
 //   0x5bec0: .x shift   .y gain      .z width fa   .w start fa
 //   0x5bec1: .x width fb  .y start fb  .z width ta   .w start ta
 //   0x5bec2: .x width tb  .y start tb
@@ -206,10 +101,9 @@ __global__ __launch_bounds__(256) void pool_spec_kernel(PoolSpecArgs a) {
   float gain = 1.f;
   int f0[2] = {0, 0}, fw[2] = {0, 0}, t0[2] = {0, 0}, tw[2] = {0, 0};
   if (b.augment) {
-    const u32x4 c{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5bec0u};
-    const u32x4 r0 = philox4x32(c, b.seed, 0xA5A5A5A5u);
-    const u32x4 r1 = philox4x32(u32x4{c.x, c.y, c.z, 0x5bec1u}, b.seed, 0xA5A5A5A5u);
-    const u32x4 r2 = philox4x32(u32x4{c.x, c.y, c.z, 0x5bec2u}, b.seed, 0xA5A5A5A5u);
+    const u32x4 r0 = pool_draw(gb, t, DRAW_SPEC, b.seed);
+    const u32x4 r1 = pool_draw(gb, t, DRAW_SPEC + 1, b.seed);
+    const u32x4 r2 = pool_draw(gb, t, DRAW_SPEC + 2, b.seed);
     shift = (int)(r0.x % (uint32_t)(2 * a.shift + 1)) - a.shift;
     gain = a.gain_lo + (a.gain_hi - a.gain_lo) * u01(r0.y);
     const uint32_t wr[4] = {r0.z, r1.x, r1.z, r2.x}, sr[4] = {r0.w, r1.y, r1.w, r2.y};
@@ -226,8 +120,7 @@ __global__ __launch_bounds__(256) void pool_spec_kernel(PoolSpecArgs a) {
     }
   }
   if (threadIdx.x == 0 && blockIdx.y == 0) {
-    b.pool_label[slot] = (int)b.labels[src];
-    b.pool_index[slot] = (int)src;
+    pool_slot_header(b, slot, src);
     if (a.params) {
       float* p = a.params + (size_t)slot * 12;
       p[0] = (float)shift;
@@ -515,18 +408,6 @@ void pool_build_launch(const PoolBuildArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(pool_take_kernel, dim3(a.P), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(pool_build_kernel, dim3(a.P), dim3(256), 0, st, a);
-}
-
-void pool_augment_launch(const PoolAugmentArgs& a, hipStream_t st) {
-  const dim3 g(a.b.P), blk(256);
-  if (a.affine && a.resize)
-    hipLaunchKernelGGL((pool_augment_kernel<true, true>), g, blk, 0, st, a);
-  else if (a.affine)
-    hipLaunchKernelGGL((pool_augment_kernel<true, false>), g, blk, 0, st, a);
-  else if (a.resize)
-    hipLaunchKernelGGL((pool_augment_kernel<false, true>), g, blk, 0, st, a);
-  else
-    hipLaunchKernelGGL((pool_augment_kernel<false, false>), g, blk, 0, st, a);
 }
 
 static int pool_spec_chunks(int P, int npx) {

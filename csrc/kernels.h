@@ -154,10 +154,12 @@ struct PoolBuildArgs {
 };
 void pool_build_launch(const PoolBuildArgs& a, hipStream_t st);
 
-// Augmentation recipe (mercury_amd/data/augment.py): Resize -> RandomCrop(pad) -> flip ->
-// RandomAffine(rotation, isotropic scale; bilinear, zeros outside) -> Normalize -> Cutout,
-// evaluated per output pixel in fp32 with no rounding between the stages.
-struct PoolAugmentArgs {
+// Image recipe (AugmentRecipe, mercury_amd/data/augment.py; pool_recipe.hip): geometry -> flip ->
+// [ColorJitter] -> /255 -> Normalize -> Cutout, evaluated per output pixel in fp32 with no
+// rounding between the stages.  The geometry is Resize -> RandomCrop(pad) -> RandomAffine
+// (rotation, isotropic scale; bilinear, zeros outside) or RandomResizedCrop (a drawn box of the
+// source, bilinear to b.H x b.W, no antialiasing).
+struct PoolRecipeArgs {
   PoolBuildArgs b;               // b.shard is [Ns][Hs][Ws][3]; b.H, b.W are the OUTPUT size
   int Hs, Ws;                    // source image size
   int resize;                    // 0: off (Hr, Wr = Hs, Ws); else the shorter side's new length
@@ -166,26 +168,19 @@ struct PoolAugmentArgs {
   float scale_lo, scale_hi;      // isotropic scale drawn from [lo, hi) (lo = hi = 1: unset)
   int cutout;                    // side of the zeroed square (0: off)
   int affine;                    // rotation / scale stage on
-  float* params;                 // optional [P][8]: dy, dx, flip, angle_deg, scale, cut_y, cut_x, 0
-};
-void pool_augment_launch(const PoolAugmentArgs& a, hipStream_t st);
-
-// Photographic recipe (AugmentRecipe with rrc or jitter, photo.hip): geometry -> flip ->
-// ColorJitter -> /255 -> Normalize -> Cutout.  The geometry is either PoolAugmentArgs' chain or
-// RandomResizedCrop (a drawn box of the source, bilinear to b.H x b.W, no antialiasing).
-struct PoolPhotoArgs {
-  PoolAugmentArgs a;             // a.b as in the sibling kernels; with rrc: a.b.pad = 0, no resize,
-                                 // no affine, (a.Hr, a.Wr) = (a.Hs, a.Ws); a.params is unused
-  int rrc;                       // RandomResizedCrop replaces Resize / RandomCrop / RandomAffine
-  float scale_lo, scale_hi;      // box area as a fraction of the source, drawn from [lo, hi)
+  int rrc;                       // RandomResizedCrop replaces Resize / RandomCrop / RandomAffine:
+                                 // b.pad = 0, no resize, no affine, (Hr, Wr) = (Hs, Ws)
+  float area_lo, area_hi;        // box area as a fraction of the source, drawn from [lo, hi)
   float ratio_lo, ratio_hi;      // box aspect w / h, log-uniform in [lo, hi)
   float log_ratio_lo, log_ratio_hi;
   float jitter[4];               // brightness, contrast, saturation, hue strengths (0: off)
-  float* params;                 // optional [P][16]: [0..7] PoolAugmentArgs' layout (rrc: top, left,
-                                 // flip, 0, 1, cut_y, cut_x, attempt), box h, w, fb, fc, fs, fh,
-                                 // order code, grey mean used by contrast
+  float* params;                 // optional [P][8]: dy, dx, flip, angle_deg, scale, cut_y, cut_x, 0
+                                 // (rrc: top, left, flip, 0, 1, cut_y, cut_x, attempt); with rrc
+                                 // or jitter [P][16]: then box h, w, fb, fc, fs, fh, order code,
+                                 // grey mean used by contrast.  The row length is a constant of
+                                 // the instantiation the launcher picks from rrc and jitter.
 };
-void pool_photo_launch(const PoolPhotoArgs& p, hipStream_t st);
+void pool_recipe_launch(const PoolRecipeArgs& p, hipStream_t st);
 
 // Spectrogram recipe (mercury_amd/data/augment.py, SpecRecipe): time shift -> gain -> frequency
 // and time masks in output coordinates, from a PLANAR bf16 shard to the NHWC8 pool.

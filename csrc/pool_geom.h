@@ -1,6 +1,6 @@
-// Device helpers shared by the pool-build kernels (importance.hip, photo.hip): which shard
-// sample fills a pool slot, the launch's zeroed slice, and the per-pixel geometry of the
-// augmentation recipes (PoolAugmentArgs).
+// Device helpers shared by the pool-build kernels (importance.hip, pool_recipe.hip): which shard
+// sample fills a pool slot, its Philox draws, the launch's zeroed slice, and the per-pixel
+// geometry of the image recipes (PoolRecipeArgs).
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -22,6 +22,27 @@ MA_DEV uint32_t pool_src(const PoolBuildArgs& a, int slot, int64_t& gb, int& t) 
                    : (uint32_t)((gb * a.batch + t) % a.Ns);
 }
 
+// Stream words of the per-slot draws: the last counter word of pool_draw.
+constexpr uint32_t DRAW_CROP = 0x5eedu;     // .x dy  .y dx  .z flip
+constexpr uint32_t DRAW_AFFINE = 0x5eeeu;   // .x angle  .y scale  .z cut_y  .w cut_x
+constexpr uint32_t DRAW_BOX = 0x5ef0u;      // + 0..4: two RandomResizedCrop box attempts each
+constexpr uint32_t DRAW_BOX_AT = 0x5ef5u;   // .x top  .y left of the accepted box
+constexpr uint32_t DRAW_COLOUR = 0x5ef8u;   // ColorJitter's four factors
+constexpr uint32_t DRAW_ORDER = 0x5ef9u;    // .x ColorJitter's order code
+constexpr uint32_t DRAW_SPEC = 0x5bec0u;    // + 0..2: pool_spec_kernel's shift, gain and masks
+
+// Slot (gb, t)'s four random words of stream `word`.
+MA_DEV u32x4 pool_draw(int64_t gb, int t, uint32_t word, uint32_t seed) {
+  return philox4x32(u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, word}, seed,
+                    0xA5A5A5A5u);
+}
+
+// The slot's label and shard index (one thread per slot calls this).
+MA_DEV void pool_slot_header(const PoolBuildArgs& b, int slot, uint32_t src) {
+  b.pool_label[slot] = (int)b.labels[src];
+  b.pool_index[slot] = (int)src;
+}
+
 MA_DEV void zero_slice(const PoolBuildArgs& a) {
   for (int j = blockIdx.x * 256 + threadIdx.x; j < a.nzero; j += gridDim.x * 256) a.zero[j] = 0.f;
 }
@@ -30,7 +51,7 @@ MA_DEV void zero_slice(const PoolBuildArgs& a) {
 // resized image, zero in the padding; the resized image itself is torch's bilinear with
 // align_corners=False over the uint8 source, every source index clamped into the image.
 template <bool RESIZE>
-MA_DEV void aug_tap(const PoolAugmentArgs& a, const uint8_t* img, int y, int x, int dy, int dx,
+MA_DEV void aug_tap(const PoolRecipeArgs& a, const uint8_t* img, int y, int x, int dy, int dx,
                     int flip, float ry, float rx, float v[3]) {
   const int xc = flip ? (a.b.W - 1 - x) : x;
   const int ys = y + dy - a.b.pad, xs = xc + dx - a.b.pad;
@@ -60,10 +81,8 @@ MA_DEV void aug_tap(const PoolAugmentArgs& a, const uint8_t* img, int y, int x, 
 // Output pixel (i, j) of the Resize -> RandomCrop(pad) -> flip -> [RandomAffine] chain, in
 // uint8 levels (0..255, float): with AFFINE, affine_grid + grid_sample (bilinear, zeros
 // padding, align_corners=False) over aug_tap; cs, sn are cos / scale and sin / scale.
-// pool_augment_kernel keeps this block written out in its own loop: called from here the
-// compiler schedules that kernel differently, and its instruction stream is pinned.
 template <bool AFFINE, bool RESIZE>
-MA_DEV void aug_pixel(const PoolAugmentArgs& a, const uint8_t* img, int H, int W, int i, int j,
+MA_DEV void aug_pixel(const PoolRecipeArgs& a, const uint8_t* img, int H, int W, int i, int j,
                       int dy, int dx, int flip, float ry, float rx, float cs, float sn,
                       float v[3]) {
   if (AFFINE) {

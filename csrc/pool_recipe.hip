@@ -1,14 +1,18 @@
-// Photographic augmentation recipes on the GPU (PoolPhotoArgs; AugmentRecipe with `rrc` or
-// `jitter`, mercury_amd/data/augment.py): one block per pool slot builds
+// Image augmentation recipes on the GPU (PoolRecipeArgs; every AugmentRecipe,
+// mercury_amd/data/augment.py, that does not take pool_build_kernel): one block per pool slot
+// builds
 //
 //     geometry -> [flip] -> [ColorJitter] -> /255 -> [Normalize] -> [Cutout]
 //
 // per output pixel from the HBM-resident uint8 shard into the NHWC8 bf16 pool, fp32 between the
-// stages.  The geometry is pool_augment_kernel's chain (pool_geom.h) or RandomResizedCrop.
+// stages.  The geometry is the Resize -> RandomCrop(pad) -> [RandomAffine] chain (pool_geom.h)
+// or RandomResizedCrop.  The crop / flip draw is pool_build_kernel's (importance.hip) word for
+// word: a crop-and-flip recipe on a shard of the output size gives the same bits from either
+// kernel.
 //
-// Draws per slot: Philox on the counter (gb, t) of the image kernels.  Stream words 0x5eed and
-// 0x5eee mean what they mean in importance.hip (dy, dx, flip; angle, scale, cut_y, cut_x) --
-// flip is r.z & 1 of the 0x5eed call for both geometries.  New words:
+// Draws per slot: Philox on the counter (gb, t) (pool_draw).  Stream word 0x5eed holds dy, dx,
+// flip and 0x5eee angle, scale, cut_y, cut_x -- flip is r.z & 1 of the 0x5eed call for both
+// geometries.  The photographic recipes (`rrc`, `jitter`) add:
 //   0x5ef0..0x5ef4: the box attempts, two per call: attempt 2k   takes .x (area) and .y (aspect),
 //                                                   attempt 2k+1 takes .z (area) and .w (aspect)
 //                   of word 0x5ef0 + k
@@ -40,7 +44,6 @@
 
 namespace {
 
-constexpr int PHOTO_PARAMS = 16;
 constexpr int OP_BRIGHT = 0, OP_CONTRAST = 1, OP_SAT = 2, OP_HUE = 3, OP_SKIP = 4;
 
 MA_DEV float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
@@ -120,23 +123,20 @@ MA_DEV void rrc_pixel(const uint8_t* img, int Ws, const PhotoBox& bx, int i, int
 }
 
 // The slot's box, by one thread (header comment).  Returns the accepted attempt, 10: fallback.
-MA_DEV int rrc_box(const PoolPhotoArgs& p, int64_t gb, int t, PhotoBox& bx) {
-  const PoolBuildArgs& b = p.a.b;
-  const int Hs = p.a.Hs, Ws = p.a.Ws;
+MA_DEV int rrc_box(const PoolRecipeArgs& p, int64_t gb, int t, PhotoBox& bx) {
+  const PoolBuildArgs& b = p.b;
+  const int Hs = p.Hs, Ws = p.Ws;
   if (b.augment) {
     const float area = (float)Hs * (float)Ws;
     for (int k = 0; k < 5; ++k) {
-      const u32x4 r = philox4x32(
-          u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5ef0u + (uint32_t)k}, b.seed,
-          0xA5A5A5A5u);
+      const u32x4 r = pool_draw(gb, t, DRAW_BOX + (uint32_t)k, b.seed);
       for (int e = 0; e < 2; ++e) {
-        const float target = area * (p.scale_lo + (p.scale_hi - p.scale_lo) * u01(e ? r.z : r.x));
+        const float target = area * (p.area_lo + (p.area_hi - p.area_lo) * u01(e ? r.z : r.x));
         const float aspect = expf(p.log_ratio_lo +
                                   (p.log_ratio_hi - p.log_ratio_lo) * u01(e ? r.w : r.y));
         const float w = rintf(sqrtf(target * aspect)), h = rintf(sqrtf(target / aspect));
         if (w >= 1.f && w <= (float)Ws && h >= 1.f && h <= (float)Hs) {
-          const u32x4 q = philox4x32(
-              u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5ef5u}, b.seed, 0xA5A5A5A5u);
+          const u32x4 q = pool_draw(gb, t, DRAW_BOX_AT, b.seed);
           bx.h = (int)h;
           bx.w = (int)w;
           bx.top = (int)(q.x % (uint32_t)(Hs - bx.h + 1));
@@ -158,15 +158,29 @@ MA_DEV int rrc_box(const PoolPhotoArgs& p, int64_t gb, int t, PhotoBox& bx) {
   return 10;
 }
 
-// GEOM 0..3: pool_augment_kernel's geometry, AFFINE << 1 | RESIZE; GEOM 4: RandomResizedCrop.
+// params[0..7] of a slot's row: the draws every recipe has.
+MA_DEV void dump_draws(float* o, int dy, int dx, int flip, float angle, float scale, int cut_y,
+                       int cut_x, int attempt) {
+  o[0] = (float)dy;
+  o[1] = (float)dx;
+  o[2] = (float)flip;
+  o[3] = angle;
+  o[4] = scale;
+  o[5] = (float)cut_y;
+  o[6] = (float)cut_x;
+  o[7] = (float)attempt;
+}
+
+// GEOM 0..3: the Resize -> RandomCrop -> [RandomAffine] chain, AFFINE << 1 | RESIZE; GEOM 4:
+// RandomResizedCrop.  PHOTO (a drawn box or colour factors): thread 0 draws them and hands them
+// to the block through LDS, and the params row has 16 floats; without, there is no LDS, no
+// barrier and the row has 8.
 template <int GEOM, bool JIT>
-__global__ __launch_bounds__(256) void pool_photo_kernel(PoolPhotoArgs p) {
+__global__ __launch_bounds__(256) void pool_recipe_kernel(PoolRecipeArgs p) {
   constexpr bool RRC = GEOM == 4, AFFINE = (GEOM & 2) != 0, RESIZE = (GEOM & 1) != 0;
-  const PoolAugmentArgs& a = p.a;
-  const PoolBuildArgs& b = a.b;
-  __shared__ float sh_f[4];
-  __shared__ int sh_i[6];
-  __shared__ float red[16];
+  constexpr bool PHOTO = RRC || JIT;
+  constexpr int PARAMS_LD = PHOTO ? 16 : 8;      // floats of a slot's params row
+  const PoolBuildArgs& b = p.b;
   const int slot = blockIdx.x;
   if (b.zero) zero_slice(b);
   int64_t gb;
@@ -175,110 +189,107 @@ __global__ __launch_bounds__(256) void pool_photo_kernel(PoolPhotoArgs p) {
   const int H = b.H, W = b.W;
   int dy = 0, dx = 0, flip = 0;
   if (!RRC) {
-    dy = (a.Hr + 2 * b.pad - H) / 2;
-    dx = (a.Wr + 2 * b.pad - W) / 2;
+    dy = (p.Hr + 2 * b.pad - H) / 2;
+    dx = (p.Wr + 2 * b.pad - W) / 2;
   }
   float angle = 0.f, scale = 1.f;
   int cut_y = 0, cut_x = 0, cut = 0;
   if (b.augment) {
-    const u32x4 r = philox4x32(u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5eedu},
-                               b.seed, 0xA5A5A5A5u);
+    const u32x4 r = pool_draw(gb, t, DRAW_CROP, b.seed);
     if (!RRC) {
-      dy = r.x % (a.Hr + 2 * b.pad - H + 1);
-      dx = r.y % (a.Wr + 2 * b.pad - W + 1);
+      dy = r.x % (p.Hr + 2 * b.pad - H + 1);
+      dx = r.y % (p.Wr + 2 * b.pad - W + 1);
     }
     flip = b.flip ? (r.z & 1) : 0;
-    const u32x4 q = philox4x32(u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5eeeu},
-                               b.seed, 0xA5A5A5A5u);
+    const u32x4 q = pool_draw(gb, t, DRAW_AFFINE, b.seed);
     if (!RRC) {
-      angle = -a.degrees + 2.f * a.degrees * u01(q.x);
-      scale = a.scale_lo + (a.scale_hi - a.scale_lo) * u01(q.y);
+      angle = -p.degrees + 2.f * p.degrees * u01(q.x);
+      scale = p.scale_lo + (p.scale_hi - p.scale_lo) * u01(q.y);
     }
     cut_y = q.z % H;
     cut_x = q.w % W;
-    cut = a.cutout;
+    cut = p.cutout;
   }
-  // the box search and the colour draws run once, in thread 0, and reach the block through LDS
-  if (threadIdx.x == 0) {
-    PhotoBox bx{0, 0, 0, 0};
-    int attempt = 0;
-    if (RRC) attempt = rrc_box(p, gb, t, bx);
-    float f[4] = {1.f, 1.f, 1.f, 0.f};
-    int code = 0, seq = OP_SKIP * 0x1111;
-    if (JIT && b.augment) {
-      const u32x4 r = philox4x32(u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5ef8u},
-                                 b.seed, 0xA5A5A5A5u);
-      const uint32_t w[3] = {r.x, r.y, r.z};
+  PhotoBox bx{0, 0, 0, 0};
+  float f[4] = {1.f, 1.f, 1.f, 0.f};
+  int seq = OP_SKIP * 0x1111;
+  if constexpr (PHOTO) {
+    // the box search and the colour draws run once, in thread 0, and reach the block through LDS
+    __shared__ float sh_f[4];
+    __shared__ int sh_i[6];
+    if (threadIdx.x == 0) {
+      int attempt = 0, code = 0;
+      if (RRC) attempt = rrc_box(p, gb, t, bx);
+      if (JIT && b.augment) {
+        const u32x4 r = pool_draw(gb, t, DRAW_COLOUR, b.seed);
+        const uint32_t w[3] = {r.x, r.y, r.z};
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float lo = fmaxf(0.f, 1.f - p.jitter[k]), hi = 1.f + p.jitter[k];
-        f[k] = lo + (hi - lo) * u01(w[k]);
+        for (int k = 0; k < 3; ++k) {
+          const float lo = fmaxf(0.f, 1.f - p.jitter[k]), hi = 1.f + p.jitter[k];
+          f[k] = lo + (hi - lo) * u01(w[k]);
+        }
+        f[3] = -p.jitter[3] + 2.f * p.jitter[3] * u01(r.w);
+        code = (int)(pool_draw(gb, t, DRAW_ORDER, b.seed).x % 24u);
       }
-      f[3] = -p.jitter[3] + 2.f * p.jitter[3] * u01(r.w);
-      const u32x4 o = philox4x32(u32x4{(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)t, 0x5ef9u},
-                                 b.seed, 0xA5A5A5A5u);
-      code = (int)(o.x % 24u);
-    }
-    if (JIT) {                        // (augment = 0: identity factors in order 0)
-      const int pick[3] = {code / 6, (code % 6) >> 1, code & 1};
-      int list = 0x3210;
-      seq = 0;
+      if (JIT) {                        // (augment = 0: identity factors in order 0)
+        const int pick[3] = {code / 6, (code % 6) >> 1, code & 1};
+        int list = 0x3210;
+        seq = 0;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int s4 = k < 3 ? 4 * pick[k] : 0;
-        const int op = (list >> s4) & 15;
-        list = (list & ((1 << s4) - 1)) | ((list >> (s4 + 4)) << s4);
-        seq |= (p.jitter[op] > 0.f ? op : OP_SKIP) << (4 * k);
+        for (int k = 0; k < 4; ++k) {
+          const int s4 = k < 3 ? 4 * pick[k] : 0;
+          const int op = (list >> s4) & 15;
+          list = (list & ((1 << s4) - 1)) | ((list >> (s4 + 4)) << s4);
+          seq |= (p.jitter[op] > 0.f ? op : OP_SKIP) << (4 * k);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sh_f[k] = f[k];
+      sh_i[0] = bx.top;
+      sh_i[1] = bx.left;
+      sh_i[2] = bx.h;
+      sh_i[3] = bx.w;
+      sh_i[4] = seq;
+      pool_slot_header(b, slot, src);
+      if (p.params) {
+        float* o = p.params + (size_t)slot * PARAMS_LD;
+        dump_draws(o, RRC ? bx.top : dy, RRC ? bx.left : dx, flip, angle, scale, cut_y, cut_x,
+                   attempt);
+        o[8] = (float)bx.h;
+        o[9] = (float)bx.w;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[10 + k] = f[k];
+        o[14] = (float)code;
       }
     }
+    __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 4; ++k) sh_f[k] = f[k];
-    sh_i[0] = bx.top;
-    sh_i[1] = bx.left;
-    sh_i[2] = bx.h;
-    sh_i[3] = bx.w;
-    sh_i[4] = seq;
-    b.pool_label[slot] = (int)b.labels[src];
-    b.pool_index[slot] = (int)src;
-    if (p.params) {
-      float* o = p.params + (size_t)slot * PHOTO_PARAMS;
-      o[0] = (float)(RRC ? bx.top : dy);
-      o[1] = (float)(RRC ? bx.left : dx);
-      o[2] = (float)flip;
-      o[3] = angle;
-      o[4] = scale;
-      o[5] = (float)cut_y;
-      o[6] = (float)cut_x;
-      o[7] = (float)attempt;
-      o[8] = (float)bx.h;
-      o[9] = (float)bx.w;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[10 + k] = f[k];
-      o[14] = (float)code;
-    }
+    for (int k = 0; k < 4; ++k) f[k] = uni_f(sh_f[k]);
+    bx.top = __builtin_amdgcn_readfirstlane(sh_i[0]);
+    bx.left = __builtin_amdgcn_readfirstlane(sh_i[1]);
+    bx.h = __builtin_amdgcn_readfirstlane(sh_i[2]);
+    bx.w = __builtin_amdgcn_readfirstlane(sh_i[3]);
+    seq = __builtin_amdgcn_readfirstlane(sh_i[4]);
+  } else if (threadIdx.x == 0) {
+    pool_slot_header(b, slot, src);
+    if (p.params)
+      dump_draws(p.params + (size_t)slot * PARAMS_LD, dy, dx, flip, angle, scale, cut_y, cut_x,
+                 0);
   }
-  __syncthreads();
-  const float f[4] = {uni_f(sh_f[0]), uni_f(sh_f[1]), uni_f(sh_f[2]), uni_f(sh_f[3])};
-  PhotoBox bx;
-  bx.top = __builtin_amdgcn_readfirstlane(sh_i[0]);
-  bx.left = __builtin_amdgcn_readfirstlane(sh_i[1]);
-  bx.h = __builtin_amdgcn_readfirstlane(sh_i[2]);
-  bx.w = __builtin_amdgcn_readfirstlane(sh_i[3]);
-  const int seq = __builtin_amdgcn_readfirstlane(sh_i[4]);
 
   // Cutout.__call__: [clip(c - L/2, 0, n), clip(c + L/2, 0, n)) in both axes (empty when off)
   const int ch = cut / 2;
   const int cy0 = cut ? max(cut_y - ch, 0) : 0, cy1 = cut ? min(cut_y + ch, H) : 0;
   const int cx0 = cut ? max(cut_x - ch, 0) : 0, cx1 = cut ? min(cut_x + ch, W) : 0;
-  const float ry = RRC ? (float)bx.h / (float)H : (float)a.Hs / (float)a.Hr;
-  const float rx = RRC ? (float)bx.w / (float)W : (float)a.Ws / (float)a.Wr;
+  const float ry = RRC ? (float)bx.h / (float)H : (float)p.Hs / (float)p.Hr;
+  const float rx = RRC ? (float)bx.w / (float)W : (float)p.Ws / (float)p.Wr;
   float cs = 1.f, sn = 0.f;
   if (AFFINE) {
     const float rad = angle * 0.017453292519943295f;
     cs = cosf(rad) / scale;
     sn = sinf(rad) / scale;
   }
-  const uint8_t* img = b.shard + (size_t)src * a.Hs * a.Ws * 3;
+  const uint8_t* img = b.shard + (size_t)src * p.Hs * p.Ws * 3;
   bf16* out = b.pool + (size_t)slot * H * W * 8;
   const int npx = H * W;
 
@@ -286,13 +297,14 @@ __global__ __launch_bounds__(256) void pool_photo_kernel(PoolPhotoArgs p) {
     i = px / W;
     j = px - i * W;
     if (RRC)
-      rrc_pixel(img, a.Ws, bx, i, flip ? W - 1 - j : j, ry, rx, v);
+      rrc_pixel(img, p.Ws, bx, i, flip ? W - 1 - j : j, ry, rx, v);
     else
-      aug_pixel<AFFINE, RESIZE>(a, img, H, W, i, j, dy, dx, flip, ry, rx, cs, sn, v);
+      aug_pixel<AFFINE, RESIZE>(p, img, H, W, i, j, dy, dx, flip, ry, rx, cs, sn, v);
   };
 
-  float m = 0.f;
-  if (JIT) {
+  float m = 0.f;                      // params[15]: written with the 16-float row only
+  if constexpr (JIT) {
+    __shared__ float red[16];
     const bool contrast = ((seq & 15) == OP_CONTRAST) | (((seq >> 4) & 15) == OP_CONTRAST) |
                           (((seq >> 8) & 15) == OP_CONTRAST) | (((seq >> 12) & 15) == OP_CONTRAST);
     if (contrast) {                   // uniform over the block
@@ -308,9 +320,9 @@ __global__ __launch_bounds__(256) void pool_photo_kernel(PoolPhotoArgs p) {
       }
       m = block_sum(acc, red) / (float)npx;
     }
-    if (threadIdx.x == 0 && p.params) p.params[(size_t)slot * PHOTO_PARAMS + 15] = m;
-  } else if (threadIdx.x == 0 && p.params) {
-    p.params[(size_t)slot * PHOTO_PARAMS + 15] = 0.f;
+    if (threadIdx.x == 0 && p.params) p.params[(size_t)slot * PARAMS_LD + 15] = m;
+  } else if (PHOTO && threadIdx.x == 0 && p.params) {
+    p.params[(size_t)slot * PARAMS_LD + 15] = 0.f;
   }
 
   for (int px = threadIdx.x; px < npx; px += 256) {
@@ -338,21 +350,21 @@ __global__ __launch_bounds__(256) void pool_photo_kernel(PoolPhotoArgs p) {
 
 }  // namespace
 
-void pool_photo_launch(const PoolPhotoArgs& p, hipStream_t st) {
-  const dim3 g(p.a.b.P), blk(256);
+template <int GEOM>
+static void recipe_launch(const PoolRecipeArgs& p, bool jit, hipStream_t st) {
+  if (jit)
+    hipLaunchKernelGGL((pool_recipe_kernel<GEOM, true>), dim3(p.b.P), dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL((pool_recipe_kernel<GEOM, false>), dim3(p.b.P), dim3(256), 0, st, p);
+}
+
+void pool_recipe_launch(const PoolRecipeArgs& p, hipStream_t st) {
   const bool jit = p.jitter[0] > 0.f || p.jitter[1] > 0.f || p.jitter[2] > 0.f || p.jitter[3] > 0.f;
-  if (p.rrc) {
-    if (jit)
-      hipLaunchKernelGGL((pool_photo_kernel<4, true>), g, blk, 0, st, p);
-    else
-      hipLaunchKernelGGL((pool_photo_kernel<4, false>), g, blk, 0, st, p);
-    return;
-  }
-  // (the binding sends a recipe with neither rrc nor jitter to pool_augment)
-  switch ((p.a.affine ? 2 : 0) | (p.a.resize ? 1 : 0)) {
-    case 3: hipLaunchKernelGGL((pool_photo_kernel<3, true>), g, blk, 0, st, p); break;
-    case 2: hipLaunchKernelGGL((pool_photo_kernel<2, true>), g, blk, 0, st, p); break;
-    case 1: hipLaunchKernelGGL((pool_photo_kernel<1, true>), g, blk, 0, st, p); break;
-    default: hipLaunchKernelGGL((pool_photo_kernel<0, true>), g, blk, 0, st, p); break;
+  switch (p.rrc ? 4 : (p.affine ? 2 : 0) | (p.resize ? 1 : 0)) {
+    case 4: recipe_launch<4>(p, jit, st); break;
+    case 3: recipe_launch<3>(p, jit, st); break;
+    case 2: recipe_launch<2>(p, jit, st); break;
+    case 1: recipe_launch<1>(p, jit, st); break;
+    default: recipe_launch<0>(p, jit, st); break;
   }
 }

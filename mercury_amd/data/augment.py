@@ -6,7 +6,7 @@ An ``AugmentRecipe`` is the data form of one ``transforms.Compose``:
              -> [Normalize] -> [Cutout]
 
 ``ops.pool_build(..., recipe=r)`` runs it on the GPU for a whole presample pool
-(``pool_augment_kernel``, ``csrc/importance.hip``); ``r.reference`` is the same
+(``pool_recipe_kernel``, ``csrc/pool_recipe.hip``); ``r.reference`` is the same
 arithmetic for one image on the CPU, with the random draws passed in, and is what the
 GPU tests compare against.  Per output pixel (i, j) of the H x W crop:
 
@@ -24,7 +24,7 @@ GPU tests compare against.  Per output pixel (i, j) of the H x W crop:
 Values stay float between the stages.  The CPU transforms round to uint8 after ``Resize``
 and after ``RandomAffine``; the unrounded result is within one uint8 level of theirs.
 
-Photographic recipes add two optional fields (``pool_photo_kernel``, ``csrc/photo.hip``; params
+Photographic recipes add two optional fields (the same kernel, with a box or colour draw; params
 are then ``PHOTO_PARAMS`` = 16 values per slot):
 
     RandomResizedCrop | the geometry above -> [flip] -> [ColorJitter] -> /255 -> [Normalize]
@@ -281,7 +281,7 @@ class AugmentRecipe:
 
     @property
     def photo(self):
-        """``rrc`` or ``jitter`` is set: ``pool_photo_kernel``'s case, ``PHOTO_PARAMS`` draws."""
+        """``rrc`` or ``jitter`` is set: the 16-float params row, ``PHOTO_PARAMS`` draws."""
         return self.rrc is not None or self.jitter is not None
 
     def with_crop(self, hw):

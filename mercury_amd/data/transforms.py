@@ -11,7 +11,7 @@ builds a whole presample pool in one HIP kernel from the HBM-resident uint8 shar
 by default RandomCrop(pad 4) + flip + CIFAR Normalize, or, given an
 ``AugmentRecipe`` (``data/augment.py``), the pipeline that recipe describes --
 Resize, RandomCrop, RandomHorizontalFlip, RandomAffine, Normalize, Cutout, and the
-photographic pair RandomResizedCrop and ColorJitter (``pool_photo_kernel``), whose
+photographic pair RandomResizedCrop and ColorJitter (``pool_recipe_kernel``), whose
 classes here run the recipe's own reference arithmetic.
 ``AugmentRecipe.from_transform`` reads a ``Compose`` of the classes below into a
 recipe (``Config.augment = 'dataset'``), so the native engine applies what the

@@ -1,4 +1,4 @@
-"""Importance-sampling kernels front-end (``csrc/importance.hip``)."""
+"""Importance-sampling kernels front-end (``csrc/importance.hip``, ``csrc/pool_recipe.hip``)."""
 from __future__ import annotations
 
 import torch
@@ -19,10 +19,10 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
     ``recipe`` (``data.augment.AugmentRecipe``) replaces pad / flip / mean / std by its own
     pipeline on a uint8 shard [Ns][Hs][Ws][3] of any size the recipe's crop fits; the pool is
     [P][h][w][8] for its crop (h, w).  A crop-and-flip recipe on a shard of the output size
-    runs the kernel above; ``force_augment_kernel`` sends it through the recipe kernel too
-    (same bits).  ``params``: an fp32 [P][8] buffer that receives each slot's draws
-    (dy, dx, flip, angle_deg, scale, cut_y, cut_x, 0).  A recipe with ``rrc`` or ``jitter``
-    (RandomResizedCrop, ColorJitter) runs ``pool_photo_kernel`` and dumps fp32 [P][16]
+    runs the kernel above; ``force_augment_kernel`` sends it through ``pool_recipe_kernel``
+    like every other recipe (same bits).  ``params``: an fp32 [P][8] buffer that receives each
+    slot's draws (dy, dx, flip, angle_deg, scale, cut_y, cut_x, 0).  A recipe with ``rrc`` or
+    ``jitter`` (RandomResizedCrop, ColorJitter) dumps fp32 [P][16]
     (``data.augment.PHOTO_PARAMS``).
 
     A ``data.augment.SpecRecipe`` (time shift, gain, frequency / time masks) takes a PLANAR bf16
@@ -49,27 +49,13 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
         recipe.check(Hs, Ws)
         pad, flip = recipe.pad, recipe.flip
         mean, std = recipe.norm()
-        if recipe.photo:
-            if force_augment_kernel:
-                raise ValueError('force_augment_kernel: a recipe with rrc or jitter has a kernel '
-                                 'of its own')
-            return _pool_photo(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed,
-                               augment, shuffle, zero, recipe, params)
-        if params is not None or force_augment_kernel or not recipe.is_legacy(Hs, Ws):
-            H, W = recipe.out_hw
-            Hr, Wr = recipe.resized_hw(Hs, Ws)
-            lo, hi = recipe.scale or (1.0, 1.0)
-            _chk(pool, torch.bfloat16, 'pool', P * H * W * 8)
-            if params is not None:
-                _chk(params, torch.float32, 'params', P * 8)
-            lib().pool_augment(ptr(shard), ptr(labels), ptr(ctrl), ptr(pool), ptr(pool_label),
-                               ptr(pool_index), Ns, Hs, Ws, H, W, P, batch, pad, int(flip),
-                               int(augment), int(shuffle), int(seed) & 0xffffffff, list(mean),
-                               [1.0 / s for s in std], stream_ptr(), ptr(zero),
-                               zero.numel() if zero is not None else 0, recipe.resize, Hr, Wr,
-                               recipe.degrees, lo, hi, recipe.cutout, int(recipe.affine),
-                               ptr(params))
-            return
+        if recipe.photo and force_augment_kernel:
+            raise ValueError('force_augment_kernel: a recipe with rrc or jitter has a kernel '
+                             'of its own')
+        if (recipe.photo or params is not None or force_augment_kernel
+                or not recipe.is_legacy(Hs, Ws)):
+            return _pool_recipe(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed,
+                                augment, shuffle, zero, recipe, params)
     elif params is not None or force_augment_kernel:
         raise ValueError('params / force_augment_kernel need a recipe')
     if not prebuilt:
@@ -85,10 +71,11 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
                      int(prebuilt), ptr(zero), zero.numel() if zero is not None else 0)
 
 
-def _pool_photo(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, augment,
-                shuffle, zero, recipe, params):
-    """A recipe with ``rrc`` or ``jitter`` (``pool_photo_kernel``, ``csrc/photo.hip``);
-    ``params`` is fp32 [P][16] (``AugmentRecipe.reference``'s layout)."""
+def _pool_recipe(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, augment,
+                 shuffle, zero, recipe, params):
+    """An ``AugmentRecipe`` through ``pool_recipe_kernel`` (``csrc/pool_recipe.hip``); ``params``
+    is fp32 [P][16] with ``rrc`` or ``jitter``, else [P][8] (``AugmentRecipe.reference``'s
+    layouts)."""
     Ns, Hs, Ws, _ = shard.shape
     H, W = recipe.out_hw
     Hr, Wr = recipe.resized_hw(Hs, Ws)
@@ -96,17 +83,17 @@ def _pool_photo(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, see
     mean, std = recipe.norm()
     _chk(pool, torch.bfloat16, 'pool', P * H * W * 8)
     if params is not None:
-        _chk(params, torch.float32, 'params', P * PHOTO_PARAMS)
-    lib().pool_photo(shard=ptr(shard), labels=ptr(labels), ctrl=ptr(ctrl), pool=ptr(pool),
-                     pool_label=ptr(pool_label), pool_index=ptr(pool_index), params=ptr(params),
-                     params_floats=params.numel() if params is not None else 0, zero=ptr(zero),
-                     nzero=zero.numel() if zero is not None else 0, stream=stream_ptr(), Ns=Ns,
-                     Hs=Hs, Ws=Ws, H=H, W=W, P=P, batch=batch, augment=int(augment),
-                     shuffle=int(shuffle), seed=int(seed) & 0xffffffff, flip=int(recipe.flip),
-                     mean=list(mean), inv_std=[1.0 / s for s in std], cutout=recipe.cutout,
-                     rrc=list(recipe.rrc or ()), jitter=list(recipe.jitter or (0.0,) * 4),
-                     pad=recipe.pad, resize=recipe.resize, Hr=Hr, Wr=Wr, degrees=recipe.degrees,
-                     scale_lo=lo, scale_hi=hi, affine=int(recipe.affine))
+        _chk(params, torch.float32, 'params', P * (PHOTO_PARAMS if recipe.photo else 8))
+    lib().pool_recipe(shard=ptr(shard), labels=ptr(labels), ctrl=ptr(ctrl), pool=ptr(pool),
+                      pool_label=ptr(pool_label), pool_index=ptr(pool_index), params=ptr(params),
+                      params_floats=params.numel() if params is not None else 0, zero=ptr(zero),
+                      nzero=zero.numel() if zero is not None else 0, stream=stream_ptr(), Ns=Ns,
+                      Hs=Hs, Ws=Ws, H=H, W=W, P=P, batch=batch, augment=int(augment),
+                      shuffle=int(shuffle), seed=int(seed) & 0xffffffff, flip=int(recipe.flip),
+                      mean=list(mean), inv_std=[1.0 / s for s in std], cutout=recipe.cutout,
+                      rrc=list(recipe.rrc or ()), jitter=list(recipe.jitter or (0.0,) * 4),
+                      pad=recipe.pad, resize=recipe.resize, Hr=Hr, Wr=Wr, degrees=recipe.degrees,
+                      scale_lo=lo, scale_hi=hi, affine=int(recipe.affine))
 
 
 def _pool_spec(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, augment,

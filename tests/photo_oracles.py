@@ -1,4 +1,4 @@
-"""CPU replay of ``pool_photo_kernel``'s per-slot draws (``csrc/photo.hip``) from the Philox
+"""CPU replay of ``pool_recipe_kernel``'s per-slot draws (``csrc/pool_recipe.hip``) from the Philox
 mirror of ``sampler_oracles``: numpy only, fp64 arithmetic on the kernel's exact fp32 uniforms.
 
 Slot ``s`` of a pool of ``P`` slots in batches of ``B`` at pool counter ``pc`` draws from the

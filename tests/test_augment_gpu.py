@@ -1,4 +1,4 @@
-"""Augmentation recipes on the GPU (``pool_augment_kernel``) against ``AugmentRecipe.reference``
+"""Augmentation recipes on the GPU (``pool_recipe_kernel``) against ``AugmentRecipe.reference``
 in fp64, fed with the draws the kernel dumped and the shard indices it wrote -- never with the
 kernel's own pixels.
 
@@ -33,8 +33,9 @@ def _noise(n, h, w, seed):
     return torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, generator=g)
 
 
-def _build(shard, labels, recipe, P, B, seed=11, pc=0, dump=True, **kw):
-    """One pool build -> (pool, labels, indices, params), everything on the host."""
+def _build(shard, labels, recipe, P, B, seed=11, pc=0, dump=True, params=None, **kw):
+    """One pool build -> (pool, labels, indices, params), everything on the host.  ``params``:
+    the device buffer to dump into, in the place of a fresh [P][8] one."""
     ops = _ops()
     H, W = recipe.out_hw
     ctrl = torch.zeros(4, dtype=torch.int64, device=DEV)
@@ -42,7 +43,9 @@ def _build(shard, labels, recipe, P, B, seed=11, pc=0, dump=True, **kw):
     pool = torch.full((P, H, W, 8), 7.0, dtype=torch.bfloat16, device=DEV)   # 7: never a result
     pl = torch.full((P,), -1, dtype=torch.int32, device=DEV)
     pi = torch.full((P,), -1, dtype=torch.int32, device=DEV)
-    params = torch.full((P, 8), -99.0, device=DEV) if dump else None
+    if params is None and dump:
+        params = torch.full((P, 8), -99.0, device=DEV)
+    dump = params is not None
     ops.pool_build(shard.to(DEV), labels.to(DEV), ctrl, pool, pl, pi, P, B, seed, recipe=recipe,
                    params=params, **kw)
     torch.cuda.synchronize()
@@ -91,6 +94,12 @@ def test_legacy_recipe_is_bit_identical():
         assert bool((d[3][:, 3] == 0).all()) and bool((d[3][:, 4] == 1).all())
 
 
+# the binding called directly: a 16x16 source, a 32x32 crop, pad 4, no rrc, no jitter
+RAW_16_TO_32 = dict(shard=0, labels=0, ctrl=0, pool=0, pool_label=0, pool_index=0, stream=0, Ns=4,
+                    Hs=16, Ws=16, H=32, W=32, P=4, batch=4, pad=4, flip=1, augment=1, shuffle=1,
+                    seed=0, mean=[0.0] * 3, inv_std=[1.0] * 3, Hr=16, Wr=16)
+
+
 def test_recipe_needs_the_uint8_shard():
     ops = _ops()
     from mercury_amd.data.augment import AugmentRecipe
@@ -104,8 +113,7 @@ def test_recipe_needs_the_uint8_shard():
         ops.pool_build(small, lab, lab, z.clone(), i, i.clone(), 4, 4, 0,
                        recipe=AugmentRecipe.cifar())
     with pytest.raises(RuntimeError, match='empty crop range'):      # the binding's own check
-        ops.lib().pool_augment(0, 0, 0, 0, 0, 0, 4, 16, 16, 32, 32, 4, 4, 4, 1, 1, 1, 0,
-                               [0.0] * 3, [1.0] * 3, 0, 0, 0, 0, 16, 16, 0.0, 1.0, 1.0, 0, 0, 0)
+        ops.lib().pool_recipe(**RAW_16_TO_32)
 
 
 FULL = dict(resize=35, crop=(32, 32), flip=True, degrees=10.0, scale=(0.9, 1.1))
@@ -135,6 +143,39 @@ def test_recipe_matches_reference(case, pc):
     assert float(params[:, 1].max()) <= Wr + 2 * r.pad - r.crop[1]
     if not r.affine:
         assert bool((params[:, 3] == 0).all()) and bool((params[:, 4] == 1).all())
+
+
+def _case(case):
+    (Ns, Hs, Ws), P, B, kw = CASES[case]
+    return _noise(Ns, Hs, Ws, 2), (torch.arange(Ns) * 7) % 10, _recipe(**kw), P, B
+
+
+@pytest.mark.parametrize('case', ['crop_only', 'full'])
+def test_params_row_is_eight_floats(case):
+    """A recipe without rrc / jitter dumps 8 floats per slot: P slots fill the first P * 8 floats
+    of a longer buffer with what a [P][8] buffer of its own receives, and touch nothing behind
+    them (a 16-float stride, or the 16-float row's grey-mean word [15], would)."""
+    shard, labels, r, P, B = _case(case)
+    want = _build(shard, labels, r, P, B, pc=1)
+    big = torch.full((P * 16 + 16,), -99.0, device=DEV)
+    got = _build(shard, labels, r, P, B, pc=1, params=big[:P * 8])
+    big = big.cpu()
+    assert bool((big[P * 8:] == -99.0).all())
+    assert torch.equal(big[:P * 8].view(torch.int32), want[3].reshape(-1).view(torch.int32))
+    assert bool((want[3] != -99.0).all()) and bool((want[3][:, 7] == 0).all())
+    assert torch.equal(got[0].view(torch.int16), want[0].view(torch.int16))
+
+
+@pytest.mark.parametrize('case', ['crop_only', 'full'])
+def test_dump_does_not_change_pixels(case):
+    """With and without a params buffer: the same pool, labels and indices, bit for bit."""
+    shard, labels, r, P, B = _case(case)
+    plain = _build(shard, labels, r, P, B, pc=1, dump=False, force_augment_kernel=True)
+    dumped = _build(shard, labels, r, P, B, pc=1, force_augment_kernel=True)
+    assert plain[3] is None and bool((dumped[3] != -99.0).all())
+    assert torch.equal(plain[0].view(torch.int16), dumped[0].view(torch.int16))
+    assert torch.equal(plain[1], dumped[1]) and torch.equal(plain[2], dumped[2])
+    assert int(plain[2].min()) >= 0 and not bool((plain[0][..., :3] == 7.0).any())
 
 
 def test_cutout_zeroes_its_square_and_nothing_else():

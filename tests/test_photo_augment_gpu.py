@@ -1,7 +1,7 @@
-"""RandomResizedCrop and ColorJitter recipes on the GPU (``pool_photo_kernel``, ``csrc/photo.hip``)
-against ``AugmentRecipe.reference`` in fp64, fed with the draws the kernel dumped and the shard
-indices it wrote -- never with the kernel's own pixels -- and the draws themselves against the
-Philox replay of ``photo_oracles``.
+"""RandomResizedCrop and ColorJitter recipes on the GPU (``pool_recipe_kernel`` with a box or
+colour draw, ``csrc/pool_recipe.hip``) against ``AugmentRecipe.reference`` in fp64, fed with the
+draws the kernel dumped and the shard indices it wrote -- never with the kernel's own pixels --
+and the draws themselves against the Philox replay of ``photo_oracles``.
 
 Tolerance, every element: |gpu - ref| <= 2^-8 |ref| + 1e-3, the bound ``test_augment_gpu``
 derives (one bf16 ulp, plus fp32 coordinates and weights: about 1e-5 after Normalize).  The
@@ -21,7 +21,7 @@ import pytest
 import torch
 
 import photo_oracles as po
-from test_augment_gpu import CASES as OLD_CASES
+from test_augment_gpu import CASES as OLD_CASES, RAW_16_TO_32
 
 pytestmark = pytest.mark.gpu
 
@@ -158,7 +158,7 @@ def test_box_draws_match_the_philox_replay():
 
 def test_whole_image_box_equals_crop_and_flip_bit_for_bit():
     """rrc = (1, 1, Ws/Hs, Ws/Hs) to the source size: the box is the image, the bilinear weights
-    are exactly 0 and 1, the flip bit is the same word -- pool_augment_kernel's bits."""
+    are exactly 0 and 1, the flip bit is the same word -- the crop + flip recipe's bits."""
     P, B = 16, 8
     shard, labels = _shard(24, HS, WS)
     a = _recipe(crop=(HS, WS), rrc=(1, 1, WS / HS, WS / HS), flip=True, mean=MEAN, std=STD)
@@ -288,7 +288,7 @@ def test_argument_checks():
     base = dict(shard=0, labels=0, ctrl=0, pool=0, pool_label=0, pool_index=0, stream=0, Ns=24,
                 Hs=HS, Ws=WS, H=24, W=20, P=16, batch=8, augment=1, shuffle=1, seed=0, flip=1,
                 mean=[0.0] * 3, inv_std=[1.0] * 3, Hr=HS, Wr=WS)
-    photo = ops.lib().pool_photo
+    photo = ops.lib().pool_recipe
     bad = [(dict(rrc=list(RRC_A), jitter=[0.4, 0.4, 0.4, 0.6]), 'hue'),
            (dict(rrc=list(RRC_A), jitter=[-0.1, 0, 0, 0]), '>= 0'),
            (dict(rrc=list(RRC_A), params=8, params_floats=16 * 8), 'P \\* 16'),
@@ -296,7 +296,7 @@ def test_argument_checks():
            (dict(rrc=[0.08, 1.0, 1.5, 0.75]), 'ratio_lo'),
            (dict(rrc=list(RRC_A), pad=4), 'replaces'),
            (dict(rrc=list(RRC_A), H=0), 'positive'),
-           (dict(), 'neither'),
+           (dict(params=8, params_floats=16 * 16), 'P \\* 8'),   # neither field: the 8-float row
            (dict(jitter=list(JIT), Hr=16, Wr=16), 'resized size'),
            (dict(jitter=list(JIT), H=64, W=64), 'empty crop range')]
     for kw, word in bad:
@@ -304,14 +304,9 @@ def test_argument_checks():
             photo(**dict(base, **kw))
     with pytest.raises(TypeError):                            # keyword arguments only
         photo(0, 0, 0, 0, 0, 0)
-    # rrc has no place in the recipe kernel's positional list: that binding is as it was
+    # a recipe with neither field set meets the same geometry checks
     with pytest.raises(RuntimeError, match='empty crop range'):
-        ops.lib().pool_augment(0, 0, 0, 0, 0, 0, 4, 16, 16, 32, 32, 4, 4, 4, 1, 1, 1, 0,
-                               [0.0] * 3, [1.0] * 3, 0, 0, 0, 0, 16, 16, 0.0, 1.0, 1.0, 0, 0, 0)
-    with pytest.raises(TypeError):
-        ops.lib().pool_augment(0, 0, 0, 0, 0, 0, 4, 16, 16, 32, 32, 4, 4, 4, 1, 1, 1, 0,
-                               [0.0] * 3, [1.0] * 3, 0, 0, 0, 0, 16, 16, 0.0, 1.0, 1.0, 0, 0, 0,
-                               list(RRC_A))
+        photo(**RAW_16_TO_32)
 
 
 class _Set(object):
