@@ -18,7 +18,15 @@ Both cells are also event-timed eagerly (``*_eager_us``, the native one through
 ops.lstm.MEASURED_NATIVE_PACKED lists the (B, H) at which native is not slower in both modes, on
 both layers and both distributions.
 
+``--proj native`` compares the native cell with itself: ``bilstm(proj='native')`` (the batched
+GEMMs in csrc/lstm_proj.hip) against ``bilstm(proj='torch')`` (torch.mm), interleaved, with the
+same graph timing; nn.LSTM is not run.  The record's ``native_*`` fields are then proj='native',
+its ``torch_*`` fields proj='torch' (``torch_proj_us`` instead of ``torch_bf16_us``), and
+``torch_min_us`` is the fastest proj='torch' run: ops.lstm.MEASURED_NATIVE_PROJ lists the
+(B, F, H) at which ``native_us <= torch_min_us`` in both modes.
+
     python bench/lstm_bench.py [--out profiles/r8/lstm/lstm_bench.jsonl] [--quick]
+    python bench/lstm_bench.py --proj native --out profiles/r20/lstm_proj/lstm_bench.jsonl
 """
 from __future__ import annotations
 
@@ -47,7 +55,7 @@ def _lens(kind, T, B, seed):
     return [int(v) for v in torch.randint(T // 2, T + 1, (B,), generator=g)]
 
 
-def _runners(T, B, F, H, train, lens=None):
+def _runners(T, B, F, H, train, lens=None, proj='torch'):
     import torch
     from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
     from mercury_amd.ops import lstm as L
@@ -68,6 +76,9 @@ def _runners(T, B, F, H, train, lens=None):
         xin = xin.detach().requires_grad_()
         f(xin, m).backward(g)
 
+    if proj == 'native':
+        return ((lambda: run(lambda a, m: L.bilstm(a, m, proj='native'), lstm, x, gout)),
+                (lambda: run(L.bilstm, lstm, x, gout)), None)
     if lens is None:
         return ((lambda: run(L.bilstm, lstm, x, gout)),
                 (lambda: run(lambda a, m: m(a)[0], ref, xb, gb)), None)
@@ -124,7 +135,11 @@ def main():
     ap.add_argument('--only', default='', help='comma-separated shape names')
     ap.add_argument('--lengths', choices=('none', 'full', 'uniform'), default='none')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--proj', choices=('torch', 'native'), default='torch',
+                    help="native: bilstm(proj='native') against bilstm(proj='torch')")
     args = ap.parse_args()
+    if args.proj == 'native' and args.lengths != 'none':
+        ap.error('--proj native is measured without lengths')
     import torch
     shapes = SHAPES[:1] if args.quick else SHAPES
     if args.only:
@@ -135,7 +150,7 @@ def main():
         for name, T, B, F, H in shapes:
             for train in (False, True):
                 lens = _lens(args.lengths, T, B, args.seed)
-                native, torch_ref, native_dev = _runners(T, B, F, H, train, lens)
+                native, torch_ref, native_dev = _runners(T, B, F, H, train, lens, args.proj)
                 tn, tt, td, en, et = [], [], [], [], []
                 hn, ht, hd = ['graph'], ['graph'], ['graph']
                 for _ in range(rounds):
@@ -154,6 +169,11 @@ def main():
                        'torch_all_us': [round(v, 1) for v in tt],
                        'device': torch.cuda.get_device_name(0)}
                 rec['native_over_torch'] = round(rec['native_us'] / rec['torch_bf16_us'], 3)
+                if args.proj == 'native':
+                    rec['proj'] = 'native'
+                    rec['torch_proj_us'] = rec.pop('torch_bf16_us')
+                    rec['torch_min_us'] = round(min(tt), 1)
+                    rec['not_slower'] = rec['native_us'] <= rec['torch_min_us']
                 if lens is not None:
                     rec.update({'lengths': args.lengths, 'seed': args.seed, 'max_len': max(lens),
                                 'mean_len': round(sum(lens) / len(lens), 1),

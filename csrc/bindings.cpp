@@ -604,6 +604,27 @@ PYBIND11_MODULE(_C, m) {
     for (a.s = s0; a.s < s1; ++a.s) lstm_step_bwd_launch(a, S(st));
     check_launch("lstm_step_bwd");
   });
+  // the layer's time-batched GEMMs (lstm_proj.hip)
+  m.def("lstm_proj_fwd", [](uintptr_t xb, uintptr_t w_ih, uintptr_t bias, uintptr_t pre, int T,
+                            int B, int F, int H, int ld, uintptr_t st) {
+    lstm_proj_launch(LstmProjArgs{P<const bf16>(xb), P<const bf16>(w_ih), P<const float>(bias),
+                                  P<float>(pre), T, B, F, H, ld, 0}, S(st));
+    check_launch("lstm_proj_fwd");
+  });
+  m.def("lstm_proj_dx", [](uintptr_t dG, uintptr_t w_ihT, uintptr_t dx, int T, int B, int F,
+                           int H, int ld, uintptr_t st) {
+    lstm_proj_launch(LstmProjArgs{P<const bf16>(dG), P<const bf16>(w_ihT), nullptr, P<float>(dx),
+                                  T, B, F, H, ld, 1}, S(st));
+    check_launch("lstm_proj_dx");
+  });
+  m.def("lstm_proj_wgrad", [](uintptr_t dG, uintptr_t xb, uintptr_t out, uintptr_t dw_ih,
+                              uintptr_t dw_hh, uintptr_t db, int T, int B, int F, int H, int ld,
+                              uintptr_t st) {
+    lstm_wgrad_launch(LstmWgradArgs{P<const bf16>(dG), P<const bf16>(xb), P<const bf16>(out),
+                                    P<float>(dw_ih), P<float>(dw_hh), P<float>(db), T, B, F, H,
+                                    ld}, S(st));
+    check_launch("lstm_proj_wgrad");
+  });
 
   // attention pooling over time (attn.hip)
   m.def("attn_pool_split", [](int T, int B) {

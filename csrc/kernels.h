@@ -420,6 +420,27 @@ struct LstmBwdArgs {                // of a forward that started from a zero sta
   const int* lens = nullptr;      // as the forward's; padded frames get dG[t] = 0 and dc = 0
 };
 void lstm_step_bwd_launch(const LstmBwdArgs& a, hipStream_t st);
+// the layer's time-batched GEMMs in the step kernels' layouts (lstm_proj.hip).  ld = F rounded up
+// to a multiple of 8; xb and w_ih have ld columns, zero in [F, ld).  Every tensor < 2^32 bytes.
+struct LstmProjArgs {
+  const bf16* a;                  // forward: xb [T*B][ld];     dx: dG [T][2][B][4H]
+  const bf16* w;                  // forward: w_ih [2][4H][ld]; dx: w_ihT [2][F][4H]
+  const float* bias;              // forward: b_ih + b_hh [2][4H]; dx: unused
+  float* out;                     // forward: pre [T][2][B][4H];   dx: dx [T*B][F]
+  int T, B, F, H, ld;
+  int dx;                         // 0: pre = xb . w_ih^T + bias, 1: dx = dG . w_ih over both d
+};
+void lstm_proj_launch(const LstmProjArgs& a, hipStream_t st);
+struct LstmWgradArgs {              // one read of dG: dW_ih, dW_hh and db of both directions
+  const bf16* dG;                 // [T][2][B][4H]
+  const bf16* xb;                 // [T*B][ld]
+  const bf16* out;                // [T][B][2H]; h_prev of (t, d) is out[t -+ 1] at column d*H
+  float* dw_ih;                   // [2][4H][F]
+  float* dw_hh;                   // [2][4H][H]
+  float* db;                      // [2][4H]
+  int T, B, F, H, ld;
+};
+void lstm_wgrad_launch(const LstmWgradArgs& a, hipStream_t st);
 // attention pooling over time (attn.hip): s = x . w, a = masked softmax_t(relu(s)),
 // rep = sum_t a x.  x / dx are addressed by element strides for t and b with the D row
 // contiguous; a block of ATTN_BLOCK_WAVES waves takes one batch row and that many shares of

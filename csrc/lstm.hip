@@ -1,8 +1,9 @@
 // Bidirectional LSTM recurrence (MyLSTM's two nn.LSTM(bidirectional=True, num_layers=1) layers,
 // `pytorch_model.py:156-242`): the sequential half of the cell as one launch per
 // time step, both directions in the same launch (blockIdx.z; direction 1 walks t = T-1 .. 0).
-// The time-batched GEMMs (x . W_ih^T, dW, dx) stay with the caller; stream order is the only
-// dependency between steps -- no persistent kernel, no grid barrier.
+// The time-batched GEMMs (x . W_ih^T, dW, dx) are the caller's: torch.matmul, or the kernels of
+// lstm_proj.hip, which read and write these layouts.  Stream order is the only dependency
+// between steps -- no persistent kernel, no grid barrier.
 //
 // forward step   gates = pre[t] + h_prev . W_hh^T   (i, f, g, o as torch orders them)
 //                c_t = f * c_prev + i * g,  h_t = o * tanh(c_t)

@@ -14,6 +14,12 @@ input or a hidden size the kernels do not tile; ``'auto'`` takes the native cell
 (batch, hidden) sizes where it was measured not slower (``ops.lstm.MEASURED_NATIVE``).  The
 parameters are the ``nn.LSTM`` modules' own in every case.
 
+``proj`` picks where the native cell's time-batched GEMMs run (``ops.lstm.bilstm``'s ``proj``):
+``'torch'`` (default) on ``torch.mm``, ``'native'`` in the HIP kernels of ``csrc/lstm_proj.hip``,
+``'auto'`` there only at the (batch, features, hidden) sizes in ``ops.lstm.MEASURED_NATIVE_PROJ``.
+It reaches only layers that take the native cell; ``cell='torch'`` with ``proj='native'`` is a
+``ValueError``.
+
 ``attn`` picks how the two attention poolings run, in the same three values (``Attention``'s
 ``impl``): the eager torch chain (default), the HIP kernels of ``csrc/attn.hip``, or those only at
 the shapes where they were measured not slower (``ops.attention.MEASURED_NATIVE``).
@@ -98,17 +104,22 @@ class Attention(nn.Module):
 
 class MyLSTM(nn.Module):
     def __init__(self, feature_dim, num_classes, hidden_dim=512, lstm_layer=2, dropout=0.2,
-                 cell='torch', attn='torch', packed=False):
+                 cell='torch', attn='torch', packed=False, proj='torch'):
         super().__init__()
         if cell not in ('torch', 'native', 'auto'):
             raise ValueError("cell must be 'torch', 'native' or 'auto', got %r" % (cell,))
         if attn not in _IMPLS:
             raise ValueError("attn must be 'torch', 'native' or 'auto', got %r" % (attn,))
+        if proj not in _IMPLS:
+            raise ValueError("proj must be 'torch', 'native' or 'auto', got %r" % (proj,))
+        if proj == 'native' and cell == 'torch':
+            raise ValueError("proj='native' needs the native cell: cell='native' or 'auto'")
         if not isinstance(packed, bool):
             raise TypeError('packed must be a bool, got %s' % type(packed).__name__)
         self.cell = cell
         self.attn = attn
         self.packed = packed
+        self.proj = proj
         self.dropout = nn.Dropout(p=dropout)
         self.lstm1 = nn.LSTM(feature_dim, hidden_dim, num_layers=1, bidirectional=True)
         self.atten1 = Attention(hidden_dim * 2, batch_first=True, impl=attn)
@@ -143,11 +154,11 @@ class MyLSTM(nn.Module):
                 raise NotImplementedError("MyLSTM(packed=True, cell='native'): the native LSTM "
                                           "cell takes lengths only on a HIP device; use "
                                           "cell='torch' or 'auto'")
-            return native.bilstm(x, lstm, lengths)
+            return native.bilstm(x, lstm, lengths, proj=self.proj)
         if self.cell == 'auto' and not (
                 x.is_cuda and (x.shape[1], lstm.hidden_size) in native.MEASURED_NATIVE):
             return lstm(x)[0]
-        return native.bilstm(x, lstm)
+        return native.bilstm(x, lstm, proj=self.proj)
 
     def forward(self, x, lengths=None):
         # x: [B, 1, F, T] spectrogram (or [B, F, T]) -> time-major [T, B, F]

@@ -117,7 +117,8 @@ from .misc import (quantize, pool2d_fwd, maxpool2d_bwd, dwconv_fwd, dwconv_dgrad
                    dwconv_bwd, dwconv_wgrad_reduce_batch, dwconv_wgrad_blocks,  # noqa: E402
                    nchw_to_nhwc8, tern_pack, tern_unpack)
 from .lstm import (lstm_step_fwd, lstm_step_bwd, pack_lstm, BiLSTMFunction, bilstm, emulate,  # noqa: E402
-                   MEASURED_NATIVE, MEASURED_NATIVE_PACKED)
+                   MEASURED_NATIVE, MEASURED_NATIVE_PACKED, MEASURED_NATIVE_PROJ,
+                   lstm_proj_fwd, lstm_proj_dx, lstm_proj_wgrad)
 from .attention import attn_pool_fwd, attn_pool_bwd, AttnPoolFunction, attn_pool  # noqa: E402
 
 __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_fwd', 'pwconv_fwd', 'stem_fwd', 'conv_dgrad', 'conv_wgrad', 'conv_bwd', 'pick_tiles',
@@ -126,6 +127,7 @@ __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_f
            'FlatOptimizer', 'optimizer_spec', 'grad_norm', 'grad_norm_plan', 'grad_norm_ranges', 'quantize', 'tern_pack', 'tern_unpack', 'pool2d_fwd', 'maxpool2d_bwd',
            'dwconv_fwd', 'dwconv_dgrad', 'dwconv_wgrad', 'dwconv_wgrad_slab_floats',
            'dwconv_bwd', 'dwconv_wgrad_reduce_batch', 'dwconv_wgrad_blocks',
-           'nchw_to_nhwc8', 'lstm_step_fwd', 'lstm_step_bwd', 'pack_lstm', 'BiLSTMFunction', 'bilstm',
+           'nchw_to_nhwc8', 'lstm_step_fwd', 'lstm_step_bwd', 'lstm_proj_fwd', 'lstm_proj_dx',
+           'lstm_proj_wgrad', 'pack_lstm', 'BiLSTMFunction', 'bilstm',
            'emulate', 'MEASURED_NATIVE', 'attn_pool_fwd', 'attn_pool_bwd', 'AttnPoolFunction',
            'attn_pool']

@@ -2,9 +2,12 @@
 
 One ``nn.LSTM(bidirectional=True, num_layers=1)`` layer, time-major ``x [T][B][F]``:
 
-* the time-batched GEMMs stay on ``torch.matmul``: ``pre = x . W_ih^T + (b_ih + b_hh)`` for all
-  T and both directions before the recurrence, and ``dW_ih``, ``dW_hh``, ``db``, ``dx`` after
-  the backward recurrence;
+* the time-batched GEMMs -- ``pre = x . W_ih^T + (b_ih + b_hh)`` for all T and both directions
+  before the recurrence, and ``dW_ih``, ``dW_hh``, ``db``, ``dx`` after the backward recurrence
+  -- run on ``torch.matmul`` by default (``proj='torch'``) and in the HIP kernels of
+  ``csrc/lstm_proj.hip`` with ``proj='native'``: those write ``pre`` straight into the
+  ``[T][2][B][4H]`` layout with the bias added, read ``dG`` in place for ``dx`` (both directions
+  in one accumulator) and produce ``dW_ih``, ``dW_hh`` and ``db`` from one read of ``dG``;
 * the sequential part runs in the HIP step kernels, one launch per time step with both
   directions in it (direction 1 walks t = T-1 .. 0).
 
@@ -44,6 +47,12 @@ MEASURED_NATIVE = frozenset({(32, 512), (320, 512)})
 # MyLSTM(packed=True, cell='auto') takes the native cell with lengths exactly there.  Empty: that
 # comparison has no recorded run yet (the step kernels alone: profiles/r13/lstm_lengths/).
 MEASURED_NATIVE_PACKED = frozenset()
+# (B, F, H) at which bench/lstm_bench.py --proj measured the layer with proj='native' not slower
+# than with proj='torch' (native's median no higher than torch's fastest run, forward alone and
+# forward + backward); bilstm(proj='auto') takes the native GEMMs exactly there.  T = 161, both
+# layer widths (profiles/r20/lstm_proj/lstm_bench.jsonl: 0.81-0.99 of proj='torch').
+MEASURED_NATIVE_PROJ = frozenset({(32, 101, 512), (320, 101, 512), (32, 1024, 512),
+                                  (320, 1024, 512)})
 
 _PARAMS = ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0',
            'weight_ih_l0_reverse', 'weight_hh_l0_reverse', 'bias_ih_l0_reverse',
@@ -136,12 +145,95 @@ def lstm_step_bwd(dout, gates, c, whhT, dG, dc, *, T, B, H, s0=0, s1=None, lengt
                         T, B, H, s0, s1, stream_ptr())
 
 
-def _pack(w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r):
+def proj_ld(F):
+    """Leading dimension of ``xb`` and ``w_ih`` for the native GEMMs: F rounded up to 8, so
+    every row starts on a 16-byte boundary; the columns past F are zeros."""
+    return (F + 7) // 8 * 8
+
+
+def _pad_cols(t, ld):
+    """t [..][F] as bf16 [..][ld] with zero columns past F (one pass over t)."""
+    if t.shape[-1] == ld:
+        return t.to(torch.bfloat16).contiguous()
+    p = torch.zeros(t.shape[:-1] + (ld,), dtype=torch.bfloat16, device=t.device)
+    p[..., :t.shape[-1]] = t
+    return p
+
+
+def _chk_proj(T, B, F, H, ld):
+    check_hidden(H)
+    if T < 1 or B < 1 or F < 1:
+        raise ValueError('native LSTM GEMMs: T, B and F must be >= 1, got T=%d B=%d F=%d' % (T, B, F))
+    if ld != proj_ld(F):
+        raise ValueError('native LSTM GEMMs: ld=%d is not F=%d rounded up to a multiple of 8'
+                         % (ld, F))
+    if max(T * B * 8 * H * 4, T * B * ld * 2, T * B * F * 4, 8 * H * ld * 2) >= 2 ** 32 - 256:
+        raise ValueError('native LSTM GEMMs: a tensor of T=%d B=%d F=%d H=%d has 2^32 bytes or '
+                         'more' % (T, B, F, H))
+
+
+def _require(fn, **tensors):
+    for n, t in tensors.items():
+        if t is None:
+            raise ValueError('%s: %s is required' % (fn, n))
+
+
+def lstm_proj_fwd(xb, w_ih, b, pre, *, T, B, F, H, ld=None):
+    """``pre[t][d][b][j] = sum_k xb[t][b][k] w_ih[d][j][k] + b[d][j]``, one launch.
+
+    xb bf16 [T*B][ld] and w_ih bf16 [2][4H][ld] with ``ld = proj_ld(F)`` and ZERO columns in
+    [F, ld); b fp32 [2][4H]; pre fp32 [T][2][B][4H], every element written."""
+    ld = proj_ld(F) if ld is None else ld
+    _chk_proj(T, B, F, H, ld)
+    _require('lstm_proj_fwd', xb=xb, w_ih=w_ih, b=b, pre=pre)
+    _chk_all(((xb, torch.bfloat16, 'xb', T * B * ld),
+              (w_ih, torch.bfloat16, 'w_ih', 8 * H * ld),
+              (b, torch.float32, 'b', 8 * H),
+              (pre, torch.float32, 'pre', T * 2 * B * 4 * H)))
+    lib().lstm_proj_fwd(ptr(xb), ptr(w_ih), ptr(b), ptr(pre), T, B, F, H, ld, stream_ptr())
+
+
+def lstm_proj_dx(dG, w_ihT, dx, *, T, B, F, H):
+    """``dx[t][b][c] = sum_d sum_j dG[t][d][b][j] w_ihT[d][c][j]``, one launch: dG bf16
+    [T][2][B][4H] read in place, w_ihT bf16 [2][F][4H], dx fp32 [T*B][F], every element
+    written."""
+    _chk_proj(T, B, F, H, proj_ld(F))
+    _require('lstm_proj_dx', dG=dG, w_ihT=w_ihT, dx=dx)
+    _chk_all(((dG, torch.bfloat16, 'dG', T * 2 * B * 4 * H),
+              (w_ihT, torch.bfloat16, 'w_ihT', 2 * F * 4 * H),
+              (dx, torch.float32, 'dx', T * B * F)))
+    lib().lstm_proj_dx(ptr(dG), ptr(w_ihT), ptr(dx), T, B, F, H, proj_ld(F), stream_ptr())
+
+
+def lstm_proj_wgrad(dG, xb, out, dw_ih, dw_hh, db, *, T, B, F, H, ld=None):
+    """The weight and bias gradients of both directions from one read of dG, one launch, no
+    atomics (two runs are bit-equal): ``dw_ih`` fp32 [2][4H][F] = dG^T . xb, ``dw_hh`` fp32
+    [2][4H][H] = dG^T . h_prev (h_prev of step t: ``out[t-1][:, :H]`` forward, ``out[t+1][:, H:]``
+    reverse, zero where that frame does not exist) and ``db`` fp32 [2][4H] = the column sums.
+    dG bf16 [T][2][B][4H]; xb bf16 [T*B][ld]; out bf16 [T][B][2H]."""
+    ld = proj_ld(F) if ld is None else ld
+    _chk_proj(T, B, F, H, ld)
+    _require('lstm_proj_wgrad', dG=dG, xb=xb, out=out, dw_ih=dw_ih, dw_hh=dw_hh, db=db)
+    _chk_all(((dG, torch.bfloat16, 'dG', T * 2 * B * 4 * H),
+              (xb, torch.bfloat16, 'xb', T * B * ld),
+              (out, torch.bfloat16, 'out', T * B * 2 * H),
+              (dw_ih, torch.float32, 'dw_ih', 2 * 4 * H * F),
+              (dw_hh, torch.float32, 'dw_hh', 2 * 4 * H * H),
+              (db, torch.float32, 'db', 2 * 4 * H)))
+    lib().lstm_proj_wgrad(ptr(dG), ptr(xb), ptr(out), ptr(dw_ih), ptr(dw_hh), ptr(db), T, B, F, H,
+                          ld, stream_ptr())
+
+
+def _pack(w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, proj=False):
     whh = torch.stack([w_hh, w_hh_r]).to(torch.bfloat16)
-    return {'w_ih': torch.stack([w_ih, w_ih_r]).to(torch.bfloat16),     # [2][4H][F]
-            'w_hh': whh,                                                # [2][4H][H]
-            'w_hhT': whh.transpose(1, 2).contiguous(),                  # [2][H][4H]
-            'b': torch.stack([b_ih + b_hh, b_ih_r + b_hh_r]).float()}   # [2][4H]
+    pk = {'w_ih': torch.stack([w_ih, w_ih_r]).to(torch.bfloat16),       # [2][4H][F]
+          'w_hh': whh,                                                  # [2][4H][H]
+          'w_hhT': whh.transpose(1, 2).contiguous(),                    # [2][H][4H]
+          'b': torch.stack([b_ih + b_hh, b_ih_r + b_hh_r]).float()}     # [2][4H]
+    if proj:        # the native GEMMs' operands (lstm_proj.hip)
+        pk['w_ihT'] = pk['w_ih'].transpose(1, 2).contiguous()           # [2][F][4H]
+        pk['w_ih_ld'] = _pad_cols(pk['w_ih'], proj_ld(w_ih.shape[1]))   # [2][4H][ld]
+    return pk
 
 
 def _lstm_params(lstm):
@@ -240,25 +332,35 @@ class BiLSTMFunction(torch.autograd.Function):
     Two more arguments may follow the parameters: ``lengths`` (an int32 tensor [B] on x's device,
     non-differentiable) and ``steps`` (an int, ``max(len_b)`` where the host knows it, else T).
     The native steps then run as ``T = steps`` on the time-major prefixes and ``out`` / ``dG``
-    beyond them are zero-filled; the batched GEMMs stay on all T frames."""
+    beyond them are zero-filled; the batched GEMMs stay on all T frames.  A third one, ``proj``
+    (bool, after ``lengths`` and ``steps``, either of which may be None), sends the batched GEMMs
+    to the kernels of ``csrc/lstm_proj.hip`` (native steps only)."""
 
     @staticmethod
     def forward(ctx, native, save, x, *params):
         ctx.n_extra = len(params) - 8
-        params, (lengths, Te) = params[:8], (params[8:] + (None, None))[:2]
+        params, (lengths, Te, proj) = params[:8], (params[8:] + (None, None, None))[:3]
         T, B, F = x.shape
         H = params[1].shape[1]
-        pk = _pack(*params)
+        proj = bool(proj)
+        if proj and not native:
+            raise ValueError('BiLSTMFunction: proj needs the native steps')
+        pk = _pack(*params, proj=proj)
         save = bool(save) and any(ctx.needs_input_grad)
         dev = x.device
-        xb = x.to(torch.bfloat16).contiguous()
+        # proj: rows of proj_ld(F) columns, zero past F, in the same single pass over x
+        xb = _pad_cols(x, proj_ld(F)) if proj else x.to(torch.bfloat16).contiguous()
         Te = T if lengths is None or Te is None else max(0, min(int(Te), T))
         if lengths is not None:
             # exact zeros in the padding of the bf16 copy: what x holds there (NaN, Inf) cannot
             # enter dW_ih, and pre at padded frames is never read
             xb = torch.where(_valid(lengths, T, dev), xb, torch.zeros((), dtype=xb.dtype, device=dev))
-        pre = _f32mm(xb.view(T * B, F), pk['w_ih'].view(8 * H, F).t()) + pk['b'].view(1, 8 * H)
-        pre = pre.view(T, B, 2, 4 * H).permute(0, 2, 1, 3).contiguous()     # [T][2][B][4H]
+        if proj:
+            pre = torch.empty(T, 2, B, 4 * H, dtype=torch.float32, device=dev)
+            lstm_proj_fwd(xb, pk['w_ih_ld'], pk['b'], pre, T=T, B=B, F=F, H=H)
+        else:
+            pre = _f32mm(xb.view(T * B, F), pk['w_ih'].view(8 * H, F).t()) + pk['b'].view(1, 8 * H)
+            pre = pre.view(T, B, 2, 4 * H).permute(0, 2, 1, 3).contiguous()     # [T][2][B][4H]
         out = torch.empty(T, B, 2 * H, dtype=torch.bfloat16, device=dev)
         gates = torch.empty(T, 2, B, 4 * H, dtype=torch.bfloat16, device=dev) if save else None
         c = torch.empty((T if save else 1), 2, B, H, dtype=torch.float32, device=dev)
@@ -275,14 +377,16 @@ class BiLSTMFunction(torch.autograd.Function):
             ctx.lengths, ctx.steps = lengths, Te
             ctx.x_dtype = x.dtype
             ctx.need_dx = ctx.needs_input_grad[2]
-            ctx.save_for_backward(xb, pk['w_ih'], pk['w_hh'], pk['w_hhT'], out, gates, c)
+            ctx.proj, ctx.F = proj, F
+            ctx.save_for_backward(xb, pk['w_ihT'] if proj else pk['w_ih'], pk['w_hh'], pk['w_hhT'],
+                                  out, gates, c)
         return out.float()
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
         xb, w_ih, w_hh, w_hhT, out, gates, c = ctx.saved_tensors
-        T, B, F = xb.shape
+        (T, B), F = xb.shape[:2], ctx.F
         H = w_hh.shape[2]
         dout = dout.float().contiguous()
         dG = torch.empty(T, 2, B, 4 * H, dtype=torch.bfloat16, device=xb.device)
@@ -296,6 +400,8 @@ class BiLSTMFunction(torch.autograd.Function):
                 lstm_step_bwd(dout, gates, c, w_hhT, dG, dc, T=Te, B=B, H=H, **kw)
         else:
             _steps_bwd_torch(dout, gates, c, w_hh, dG, T, B, H, **kw)
+        if ctx.proj:        # (w_ih is the transposed copy here)
+            return BiLSTMFunction._backward_proj(ctx, xb, w_ih, out, dG, T, B, F, H)
         # the time-batched GEMMs: bf16 operands, fp32 accumulation
         x2 = xb.view(T * B, F)
         dx = None
@@ -318,6 +424,23 @@ class BiLSTMFunction(torch.autograd.Function):
             dx = dx.view(T, B, F).to(ctx.x_dtype)
         return (None, None, dx, *grads) + (None,) * ctx.n_extra
 
+    @staticmethod
+    def _backward_proj(ctx, xb, w_ihT, out, dG, T, B, F, H):
+        dev = xb.device
+        dx = None
+        if ctx.need_dx:
+            dx = torch.empty(T * B, F, dtype=torch.float32, device=dev)
+            lstm_proj_dx(dG, w_ihT, dx, T=T, B=B, F=F, H=H)
+            dx = dx.view(T, B, F).to(ctx.x_dtype)
+        dw_ih = torch.empty(2, 4 * H, F, dtype=torch.float32, device=dev)
+        dw_hh = torch.empty(2, 4 * H, H, dtype=torch.float32, device=dev)
+        db = torch.empty(2, 4 * H, dtype=torch.float32, device=dev)
+        lstm_proj_wgrad(dG, xb, out, dw_ih, dw_hh, db, T=T, B=B, F=F, H=H)
+        grads = []
+        for d in (0, 1):
+            grads += [dw_ih[d], dw_hh[d], db[d], db[d].clone()]
+        return (None, None, dx, *grads) + (None,) * ctx.n_extra
+
 
 def _host_steps(lengths, T):
     """max(len_b) where it costs nothing (a list or a CPU tensor), else None."""
@@ -330,30 +453,53 @@ def _host_steps(lengths, T):
     return max(0, min(max((int(v) for v in lengths), default=0), T))
 
 
-def _apply(native, x, lstm, lengths=None):
+def _apply(native, x, lstm, lengths=None, proj=False):
     params = _lstm_params(lstm)
     if x.dim() != 3 or x.shape[2] != lstm.input_size:
         raise ValueError('expected x [T][B][%d], got %s' % (lstm.input_size, tuple(x.shape)))
+    tail = (True,) if proj else ()
     if lengths is None:
-        return BiLSTMFunction.apply(native, torch.is_grad_enabled(), x, *params)
+        if proj:
+            tail = (None, None, True)
+        return BiLSTMFunction.apply(native, torch.is_grad_enabled(), x, *params, *tail)
     T, B = x.shape[:2]
     steps = _host_steps(lengths, T)
     lengths = _lengths_tensor(lengths, B, x.device)
     return BiLSTMFunction.apply(native, torch.is_grad_enabled(), x, *params, lengths,
-                                T if steps is None else steps)
+                                T if steps is None else steps, *tail)
 
 
-def bilstm(x, lstm, lengths=None):
+def _native_proj(proj, x, lstm):
+    """Whether ``bilstm`` sends the batched GEMMs to lstm_proj.hip; ``'native'`` refuses here,
+    before any launch, what the kernels refuse."""
+    if proj not in ('torch', 'native', 'auto'):
+        raise ValueError("proj must be 'torch', 'native' or 'auto', got %r" % (proj,))
+    if proj == 'torch' or x.dim() != 3:
+        return False
+    T, B, F = x.shape
+    if proj == 'auto':
+        return (B, F, lstm.hidden_size) in MEASURED_NATIVE_PROJ
+    _chk_proj(T, B, F, lstm.hidden_size, proj_ld(F))
+    return True
+
+
+def bilstm(x, lstm, lengths=None, proj='torch'):
     """The layer's output [T][B][2H] through the HIP step kernels; differentiable in x and the
     module's parameters.  Refuses a CPU input or an unsupported hidden size (``ValueError``).
     ``lengths``: None, a list, a CPU tensor or a device tensor of B integers (no host sync for a
     device tensor; values are clamped to [0, T]): packed-sequence semantics, ``out`` and ``dx``
     exactly 0 at ``t >= len_b``.  Lengths known on the host also cut the launches to
-    ``max(len_b)`` steps; the result has the same bits either way."""
+    ``max(len_b)`` steps; the result has the same bits either way.
+
+    ``proj``: where the time-batched GEMMs (``pre``, ``dx``, ``dW_ih``, ``dW_hh``, ``db``) run.
+    ``'torch'`` (default): ``torch.mm``.  ``'native'``: the kernels of ``csrc/lstm_proj.hip``, with
+    and without lengths; a ``ValueError`` on a shape they refuse (an empty dimension, a tensor of
+    2^32 bytes or more), never a substitute.  ``'auto'``: native only at the (B, F, H) in
+    ``MEASURED_NATIVE_PROJ``."""
     check_hidden(lstm.hidden_size)
     if not x.is_cuda or not lstm.weight_hh_l0.is_cuda:
         raise ValueError('native LSTM cell: x and the module must be on a HIP device')
-    return _apply(True, x, lstm, lengths)
+    return _apply(True, x, lstm, lengths, _native_proj(proj, x, lstm))
 
 
 def emulate(x, lstm, lengths=None):
