@@ -24,6 +24,15 @@ def worst(f, base_row=0):
     return ways
 
 
+def worst_b32(addr):
+    """ds_read_b32 of a whole wave: the most lanes on one of the 64 four-byte banks, for the
+    word address ``addr(lane)`` (lanes reading the same word share one access)."""
+    banks = {}
+    for lane in range(64):
+        banks.setdefault(addr(lane) % 64, set()).add(addr(lane))
+    return max(len(v) for v in banks.values())
+
+
 if __name__ == '__main__':
     for name, f in (('c ^ ((r>>1)&3)', lambda r: (r >> 1) & 3), ('none', lambda r: 0)):
         print('%-16s worst conflict: %d-way' % (name, max(worst(f, b) for b in range(0, 256, 16))))

@@ -20,12 +20,43 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def main_f32(args):
+    """fp32 matrix rate: 32 MFMAs of 16x16x4 (65,536 FLOP) per wave per trip, 4 waves per block."""
+    import ctypes
+    import torch
+    from mercury_amd import _build
+    from mercury_amd.ops import ptr, stream_ptr
+    L = ctypes.CDLL(_build.TOOLS if os.path.exists(_build.TOOLS)
+                    else _build.build_tools(verbose=False))
+    L.ubench_mfma_f32.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    out = torch.empty(args.grid * 256, device='cuda')
+    flop = 65536.0 * 4 * args.grid * args.trips
+    t_end = time.time() + 2.0
+    while time.time() < t_end:
+        L.ubench_mfma_f32(args.trips, args.grid, ptr(out), stream_ptr())
+    torch.cuda.synchronize()
+    tf = []
+    for _ in range(args.rounds):
+        t0 = time.perf_counter()
+        L.ubench_mfma_f32(args.trips, args.grid, ptr(out), stream_ptr())
+        torch.cuda.synchronize()
+        tf.append(flop / (time.perf_counter() - t0) / 1e12)
+    tf.sort()
+    print(json.dumps({'bench': 'mfma_f32_16x16x4', 'grid': args.grid, 'trips': args.trips,
+                      'tflops_median': round(tf[len(tf) // 2], 1), 'tflops_min': round(tf[0], 1),
+                      'tflops_max': round(tf[-1], 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--trips', type=int, default=20000)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--grid', type=int, default=256)
+    ap.add_argument('--f32', action='store_true',
+                    help='time v_mfma_f32_16x16x4_f32 alone (operands in registers)')
     args = ap.parse_args()
+    if args.f32:
+        return main_f32(args)
     import ctypes
     import torch
     from mercury_amd import _build

@@ -1,0 +1,185 @@
+"""Cost of the waveform front end (csrc/pool_wave.hip pool_wave_kernel).
+
+    python bench/wave_bench.py pool [--out FILE] [--runs R] [--ns N]
+    python bench/wave_bench.py step [--out FILE] [--steps K] [--warmup W] [--runs R] [--ns N]
+    python bench/wave_bench.py banks
+
+``pool``: ``bench/gtime.py`` time of one pool build of 101 x 161 log-spectrograms (n_fft 200, hop
+100, 16000-sample int16 clips) at P = 320 and P = 32 (batch 32): ``pool_wave_kernel`` as the
+identity, with shift + gain, and as the full recipe, with the launcher's own frame chunks and with
+fixed numbers of them, beside ``pool_spec_kernel``'s identity on the same-sized planar bf16
+spectrogram shard.  Every call advances the pool counter.  Interleaved, ``--runs`` times.
+
+``step``: the vgg11-speech preset as ``bench.py`` builds it (a spectrogram shard, no recipe)
+against the same network fed from a synthetic int16 waveform shard through the full recipe,
+ms/step, interleaved, ``--runs`` times.
+
+``banks`` (no GPU): LDS bank conflicts of the A-operand read ``lds[(f0 + lane % 16) * hop + 4 k +
+lane / 16]`` for a few hops -- the worst number of lanes of a wave on one of the 64 banks, by
+the bank model of ``bench/lds_swizzle_check.py`` (``worst_b32``).
+One JSON line per measurement, appended to ``--out`` and printed.
+"""
+from __future__ import annotations
+
+import os
+if int(os.environ.get('GPU_MAX_HW_QUEUES') or 0) < 16:   # before torch loads HIP
+    os.environ['GPU_MAX_HW_QUEUES'] = '16'
+
+import argparse
+import json
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'bench'))
+
+SHIFT_GAIN = 'wave:nfft=200,hop=100,shift=1600,gain=0.8:1.2,norm=-5:4'
+FULL = SHIFT_GAIN + ',noise=0.8x0.1,fmask=2x10,tmask=2x20'
+L, H, W = 16000, 101, 161
+
+
+def emit(rec, out):
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'a') as f:
+            f.write(line + '\n')
+
+
+def _clips(n, length, dev, seed):
+    import torch
+    g = torch.Generator(device=dev).manual_seed(seed)
+    out = torch.empty(n, length, dtype=torch.int16, device=dev)
+    for s0 in range(0, n, 2048):
+        blk = torch.randn(min(2048, n - s0), length, device=dev, generator=g)
+        out[s0:s0 + 2048] = (blk * 0.2).clamp(-1, 1).mul(32767).to(torch.int16)
+    return out
+
+
+def bench_pool(args):
+    import torch
+    from gtime import gtime
+    from mercury_amd import ops
+    from mercury_amd.data.augment import SpecRecipe, WaveRecipe
+    from mercury_amd.ops.importance import _pool_spec, _pool_wave
+    ops.lib()
+    dev = 'cuda'
+    Ns, B = args.ns, 32
+    shard, bank = _clips(Ns, L, dev, 8), _clips(6, 60 * L, dev, 9)
+    planar = torch.randn(min(Ns, 4096), 1, H, W, device=dev).bfloat16()
+    labels = torch.randint(0, 30, (Ns,), device=dev)
+    recipes = {'identity': WaveRecipe.parse('wave:nfft=200,hop=100,norm=-5:4'),
+               'shift+gain': WaveRecipe.parse(SHIFT_GAIN), 'full': WaveRecipe.parse(FULL)}
+    for P in (320, 32):
+        ctrl = torch.zeros(4, dtype=torch.int64, device=dev)
+        pool = torch.zeros(P, H, W, 8, dtype=torch.bfloat16, device=dev)
+        pl = torch.zeros(P, dtype=torch.int32, device=dev)
+        pi = torch.zeros(P, dtype=torch.int32, device=dev)
+
+        def wave(recipe, chunks):
+            def fn():
+                _pool_wave(shard, bank if recipe.noise else None, labels, ctrl, pool, pl, pi, P,
+                           B, 7, True, True, None, recipe, None, chunks=chunks)
+                ctrl[0:1].add_(1)
+            return fn
+
+        def spec():
+            _pool_spec(planar, labels[:planar.shape[0]], ctrl, pool, pl, pi, P, B, 7, True, True,
+                       None, SpecRecipe(), None)
+            ctrl[0:1].add_(1)
+
+        def tick():                     # what every variant pays beside its kernel
+            ctrl[0:1].add_(1)
+
+        variants = [('pool_spec_kernel identity', 0, spec), ('counter increment alone', 0, tick)]
+        for name, r in recipes.items():
+            for chunks in ((0, 2, 3, 4, 6, 11) if name == 'full' else (0,)):
+                variants.append(('pool_wave_kernel %s' % name, chunks, wave(r, chunks)))
+        for run in range(args.runs):
+            for label, chunks, fn in variants:
+                ctrl.zero_()
+                us = gtime(fn, reps=16)
+                rec = {'bench': 'wave_pool', 'run': run, 'P': P, 'Ns': Ns, 'variant': label,
+                       'chunks': chunks, 'us': round(us, 3)}
+                if 'wave' in label:     # the padded GEMM: 176 frames x 200 x (2 x 112) columns
+                    rec['gflop'] = round(P * 2 * 176 * 200 * 2 * 112 / 1e9, 3)
+                emit(rec, args.out)
+
+
+def bench_step(args):
+    import numpy as np
+    import torch
+    from bench import PRESETS, preset_data
+    from mercury_amd.data.augment import WaveRecipe
+    from mercury_amd.engine.native import NativeEngine
+    from mercury_amd.models import build_model
+    pre = PRESETS['vgg11-speech']
+    hw, x, y = preset_data(pre)
+    clips = _clips(args.ns, L, 'cuda', 8)
+    bank = _clips(6, 4 * L, 'cuda', 9)
+    yw = np.arange(args.ns) % pre['classes']
+
+    def one(recipe):
+        torch.manual_seed(1234)
+        net = build_model(pre['model'], pre['classes']).to('cuda')
+        eng = NativeEngine(net, 'cuda', pre['batch'], 10, optimizer='adam', lr=0.001, seed=7,
+                           importance=True, world_size=1, use_graphs=True, image_hw=hw,
+                           augment=recipe)
+        if recipe is None:
+            eng.set_shard(x, y)
+        else:
+            eng.set_shard(clips, yw, noise=bank)
+        eng.prime()
+        eng.step()
+        eng.build_graphs()
+        for _ in range(args.warmup):
+            eng.step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            eng.step()
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3 / args.steps
+        m = eng.read_meters()
+        eng.close()
+        return ms, m['loss_sum'] / max(m['count'], 1)
+
+    full = WaveRecipe.parse(FULL)
+    res = {'spectrogram shard': [], 'wave shard': []}
+    for r in range(args.runs):
+        for name, recipe in (('spectrogram shard', None), ('wave shard', full)):
+            ms, loss = one(recipe)
+            res[name].append(ms)
+            emit({'bench': 'wave_step', 'run': r, 'shard': name, 'steps': args.steps,
+                  'warmup': args.warmup, 'ms_per_step': round(ms, 4),
+                  'train_loss': round(loss, 4)}, args.out)
+    emit({'bench': 'wave_step_summary',
+          **{'median_ms %s' % k: round(float(np.median(v)), 4) for k, v in res.items()},
+          **{'max_minus_min_us %s' % k: round((max(v) - min(v)) * 1e3, 2)
+             for k, v in res.items()}}, args.out)
+
+
+def bench_banks(args):
+    from lds_swizzle_check import worst_b32
+    for hop in (100, 160, 128, 16, 7, 80, 64):
+        worst = max(worst_b32(lambda lane: (lane % 16) * hop + 4 * k + lane // 16)
+                    for k in range(4))
+        emit({'bench': 'wave_banks', 'hop': hop, 'worst_lanes_per_bank': worst}, args.out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('mode', choices=('pool', 'step', 'banks'))
+    ap.add_argument('--out', default='')
+    ap.add_argument('--steps', type=int, default=100)
+    ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--runs', type=int, default=3)
+    ap.add_argument('--ns', type=int, default=4096)
+    args = ap.parse_args()
+    {'pool': bench_pool, 'step': bench_step, 'banks': bench_banks}[args.mode](args)
+
+
+if __name__ == '__main__':
+    main()

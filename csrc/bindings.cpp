@@ -770,6 +770,44 @@ PYBIND11_MODULE(_C, m) {
     pool_spec_launch(a, S(st));
     check_launch("pool_spec");
   });
+  // waveform recipes (pool_wave.hip): keyword arguments only; the launcher checks the shapes
+  m.def("pool_wave_ksteps", &pool_wave_ksteps);
+  m.def("pool_wave", [](uintptr_t shard, uintptr_t noise, uintptr_t tab, long long tab_floats,
+                        uintptr_t labels, uintptr_t ctrl, uintptr_t pool, uintptr_t pool_label,
+                        uintptr_t pool_index, uintptr_t params, uintptr_t zero, int nzero,
+                        uintptr_t st, int f32, int Ns, int L, int Nn, int Ln, int n_fft, int hop,
+                        int Pn, int batch, int augment, int shuffle, uint32_t seed, int shift,
+                        float gain_lo, float gain_hi, float noise_p, float vol_max, float eps,
+                        float log_a, float log_b, int fmask_n, int fmask_max, int tmask_n,
+                        int tmask_max, float fill, int chunks) {
+    if (!std::isfinite(gain_lo) || !std::isfinite(gain_hi) || gain_hi < gain_lo ||
+        !std::isfinite(fill) || !std::isfinite(log_a) || !std::isfinite(log_b) ||
+        !(noise_p >= 0.f && noise_p <= 1.f) || !(vol_max >= 0.f) || !std::isfinite(vol_max))
+      throw std::invalid_argument("pool_wave: gain, fill, norm and noise must be finite, "
+                                  "gain lo <= hi, noise p in [0, 1], vol_max >= 0");
+    if (n_fft < 2 || hop < 1 || L < 1 || L >= (1 << 30) || shift < 0 || shift >= (1 << 30))
+      throw std::invalid_argument("pool_wave: n_fft, hop, L positive; L and shift below 2^30");
+    const int F = n_fft / 2 + 1;
+    PoolWaveArgs a{pool_build_args(shard, labels, ctrl, pool, pool_label, pool_index, Ns, F,
+                                   1 + L / hop, Pn, batch, 0, 0, augment, shuffle, seed,
+                                   {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, 0, zero, nzero),
+                   P<const void>(noise), P<const float>(tab), tab_floats, f32, L, Nn, Ln, n_fft,
+                   hop, (F + 15) & ~15, shift, gain_lo, gain_hi, noise_p, vol_max, eps, log_a,
+                   log_b, fmask_n, fmask_max, tmask_n, tmask_max, fill, P<float>(params), chunks,
+                   0, 0};
+    pool_wave_launch(a, S(st));
+    check_launch("pool_wave");
+  }, py::kw_only(), py::arg("shard"), py::arg("noise") = 0, py::arg("tab"),
+     py::arg("tab_floats"), py::arg("labels"), py::arg("ctrl"), py::arg("pool"),
+     py::arg("pool_label"), py::arg("pool_index"), py::arg("params") = 0, py::arg("zero") = 0,
+     py::arg("nzero") = 0, py::arg("stream"), py::arg("f32"), py::arg("Ns"), py::arg("L"),
+     py::arg("Nn") = 0, py::arg("Ln") = 0, py::arg("n_fft"), py::arg("hop"), py::arg("P"),
+     py::arg("batch"), py::arg("augment"), py::arg("shuffle"), py::arg("seed"),
+     py::arg("shift") = 0, py::arg("gain_lo") = 1.f, py::arg("gain_hi") = 1.f,
+     py::arg("noise_p") = 0.f, py::arg("vol_max") = 0.f, py::arg("eps"), py::arg("log_a") = 1.f,
+     py::arg("log_b") = 0.f, py::arg("fmask_n") = 0, py::arg("fmask_max") = 0,
+     py::arg("tmask_n") = 0, py::arg("tmask_max") = 0, py::arg("fill") = 0.f,
+     py::arg("chunks") = 0);
   m.def("is_sample", [](uintptr_t losses, uintptr_t ema, uintptr_t ctrl, uintptr_t idx, uintptr_t w,
                         uintptr_t meters, int Pn, int B, int group, int importance, float alpha,
                         float ema_alpha, uint32_t seed, uintptr_t st, int alias, uintptr_t gl,

@@ -198,6 +198,32 @@ struct PoolSpecArgs {
 };
 void pool_spec_launch(const PoolSpecArgs& a, hipStream_t st);
 
+// Waveform recipe (mercury_amd/data/augment.py, WaveRecipe; pool_wave.hip): shift, gain and noise
+// mix on the raw clip -> reflect-padded windowed DFT on the fp32 matrix cores -> log power ->
+// masks, from an int16 / float32 shard [Ns][L] to the NHWC8 pool [P][F][T][8].
+struct PoolWaveArgs {
+  PoolBuildArgs b;               // b.shard is [Ns][L]; b.H = F = n_fft/2 + 1 bins, b.W = T frames
+  const void* noise;             // optional [Nn][Ln] background clips of the shard's dtype
+  const float* tab;              // [4*ksteps][2*F16]: window-folded cos | -sin (pool_wave.hip)
+  long long tab_floats;
+  int f32;                       // shard and noise are float32 (else int16 PCM, read as x / 32768)
+  int L, Nn, Ln, n_fft, hop, F16;
+  int shift;                     // shift in samples drawn from [-shift, shift]
+  float gain_lo, gain_hi;        // gain drawn from [lo, hi) (lo = hi = 1: unset, exactly 1.0f)
+  float noise_p, vol_max;        // noise mixed in with probability p at a volume from [0, vol_max)
+  float eps, log_a, log_b;       // y = log_a * ln(re^2 + im^2 + eps) + log_b
+  int fmask_n, fmask_max;        // frequency masks: how many (0..2), widths drawn from [0, max]
+  int tmask_n, tmask_max;        // time masks likewise
+  float fill;                    // value of masked pixels, in output units (rounded to bf16 once)
+  float* params;                 // optional [P][16]: shift, gain, noise_on, clip, off, vol, f0a,
+                                 //   fwa, f0b, fwb, t0a, twa, t0b, twb, 0, 0
+  int chunks;                    // frame chunks per slot (grid.y); 0: the launcher's measured rule
+  int tiles_per_chunk, lds_words;   // (filled in by the launcher)
+};
+// throws std::invalid_argument on a shape the kernel cannot run (never a substitute)
+void pool_wave_launch(const PoolWaveArgs& a, hipStream_t st);
+int pool_wave_ksteps(int n_fft);   // K steps (of 4 samples) the table is padded to; 0: unsupported
+
 struct IsSampleArgs {
   const float* losses;           // [P]
   float* ema;                    // [0] value, [1] initialised flag (device-resident EMAverage)

@@ -1,4 +1,4 @@
-// Device helpers shared by the pool-build kernels (importance.hip, pool_recipe.hip): which shard
+// Device helpers shared by the pool-build kernels (importance.hip, pool_recipe.hip, pool_wave.hip): which shard
 // sample fills a pool slot, its Philox draws, the launch's zeroed slice, and the per-pixel
 // geometry of the image recipes (PoolRecipeArgs).
 #pragma once
@@ -30,6 +30,7 @@ constexpr uint32_t DRAW_BOX_AT = 0x5ef5u;   // .x top  .y left of the accepted b
 constexpr uint32_t DRAW_COLOUR = 0x5ef8u;   // ColorJitter's four factors
 constexpr uint32_t DRAW_ORDER = 0x5ef9u;    // .x ColorJitter's order code
 constexpr uint32_t DRAW_SPEC = 0x5bec0u;    // + 0..2: pool_spec_kernel's shift, gain and masks
+constexpr uint32_t DRAW_WAVE = 0x5bec8u;    // + 0..3: pool_wave_kernel's shift, gain, noise and masks
 
 // Slot (gb, t)'s four random words of stream `word`.
 MA_DEV u32x4 pool_draw(int64_t gb, int t, uint32_t word, uint32_t seed) {

@@ -135,7 +135,33 @@ __global__ __launch_bounds__(256, 1) void mfma_loop_kernel(const bf16* __restric
   }
 }
 
+// v_mfma_f32_16x16x4_f32 issue rate (the waveform DFT's instruction): 8 independent accumulator
+// chains per wave, operands in registers, 32 MFMAs = 65,536 FLOP per wave per trip.
+__global__ __launch_bounds__(256, 1) void mfma_f32_loop_kernel(int trips, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  float a = 1.f + lane * 0x1p-10f, b = 1.f - lane * 0x1p-11f;
+  f32x4 acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < trips; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[i], 0, 0, 0);
+    asm volatile("" : "+v"(a), "+v"(b));   // (opaque operands: the loop body stays in the loop)
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
+  out[blockIdx.x * 256 + threadIdx.x] = s;
+}
+
 }  // namespace
+
+extern "C" int ubench_mfma_f32(int trips, int grid, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(mfma_f32_loop_kernel, dim3(grid), dim3(256), 0, st, trips, out);
+  return 1;
+}
 
 // shape 16 / 32, lds 0 / 1; src: >= 2 MB of bf16 (random), out: grid * 256 floats
 // C ABI: this file is its own shared object (mercury_amd/_tools.so, loaded by ctypes from

@@ -44,6 +44,8 @@ class Config:
     #                                 jitter=0.4:0.4:0.4:0.1' (RandomResizedCrop, ColorJitter)
     #                                 | a SpecRecipe.parse spec for float [N][C][F][T] datasets,
     #                                 e.g. 'spec:shift=8,fmask=2x10,tmask=2x20,gain=0.8:1.2'
+    #                                 | a WaveRecipe.parse spec for raw-clip [N][L] datasets, e.g.
+    #                                 'wave:nfft=200,hop=100,shift=1600,gain=0.8:1.2,noise=0.8x0.1'
     # model / optimisation
     model: str = 'resnet18'
     optimizer: str = 'adam'

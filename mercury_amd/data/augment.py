@@ -51,6 +51,8 @@ are then ``PHOTO_PARAMS`` = 16 values per slot):
 
 ``SpecRecipe`` (below) is the recipe of float spectrogram inputs: time shift, gain, frequency
 and time masks, run by ``pool_spec_kernel`` from a planar bf16 shard and exact to the bit.
+``WaveRecipe`` is the recipe of raw waveforms: shift, gain and background noise on the clip, then
+the log-spectrogram, run by ``pool_wave_kernel`` (fp32 MFMA DFT) from an int16 / float32 shard.
 """
 from __future__ import annotations
 
@@ -649,4 +651,267 @@ class SpecRecipe:
         v = torch.where(live.unsqueeze(0), v, fill)
         out = torch.zeros(H, W, 8, dtype=dtype)
         out[:, :, :C] = v.permute(1, 2, 0)
+        return out
+
+
+# ---------------------------------------------------------------------- waveforms
+WAVE_PARAMS = 16     # shift, gain, noise_on, clip, off, vol, f0a, fwa, f0b, fwb, t0a, twa, t0b,
+#                      twb, 0, 0
+
+
+def _fpair(v, name, what='(lo, hi)'):
+    if v is None:
+        return None
+    if len(v) != 2:
+        raise ValueError('WaveRecipe: %s is %s' % (name, what))
+    v = (float(v[0]), float(v[1]))
+    if not all(math.isfinite(g) for g in v):
+        raise ValueError('WaveRecipe: %s must be finite, got %r' % (name, v))
+    return v
+
+
+@dataclass(frozen=True)
+class WaveRecipe:
+    """Waveform augmentation and the log-spectrogram front end for raw clips ``x[0..L)``, run by
+    ``pool_wave_kernel`` (``csrc/pool_wave.hip``) on an int16 or float32 shard [Ns][L] for a whole
+    pool: ``ops.pool_build(..., recipe=r, noise=bank)``.  int16 PCM is read as ``x / 32768``,
+    float32 as is (finite values only); the noise bank ``[Nn][Ln]``, ``Ln >= L``, has the
+    shard's dtype.
+
+    One pool slot, given its draws:
+
+    1. ``xa[j] = gain * x[j - s]`` where ``0 <= j - s < L``, else 0; with noise on, then
+       ``xa[j] = fma(vol, noise[clip][off + j], xa[j])`` -- fp32, one multiply and one FUSED
+       multiply-add in the kernel (``reference`` does both in fp64, where the two agree);
+    2. centre padding of ``xa`` by ``n_fft / 2`` on each side, reflected
+       (``torch.stft(center=True, pad_mode='reflect')``), which needs ``L > n_fft / 2``;
+    3. ``X[t][k] = sum_n w[n] xp[t*hop + n] exp(-2 pi i k n / W)``, ``w`` the periodic Hann
+       window, ``t < T = 1 + L // hop`` frames, ``k < F = W/2 + 1`` bins;
+    4. ``y[k][t] = a ln(re^2 + im^2 + eps) + b`` with ``a = 1/std``, ``b = -mean/std`` of ``norm``
+       (1 and 0 without);
+    5. ``fill`` (output units) where ``k`` lies in a frequency band or ``t`` in a time band,
+       ``SpecRecipe``'s width and start formulas on (F, T);
+    6. one rounding to bf16, channel 0 of the NHWC8 pixel (row k, column t); channels 1..7 +0.
+
+    Draws, per pool slot (Philox on the image kernels' counter ``(gb, t)``, stream words
+    0x5bec8..0x5becb of its own): ``s = r % (2*shift + 1) - shift``; ``gain = fma(hi - lo,
+    u01(r), lo)``, one rounding; noise on iff ``u01(r) < p``, then ``clip = r % Nn``, ``off = r % (Ln - L + 1)``,
+    ``vol = vol_max * u01(r)``; masks as ``SpecRecipe``.  ``augment=False`` draws the identity
+    (no shift, gain 1, no noise, no masks), so evaluation still gets its spectrogram."""
+    n_fft: int = 200
+    hop: int = 100
+    shift: int = 0                                  # maximum shift in samples
+    gain: Optional[Tuple[float, float]] = None      # (lo, hi)
+    noise: Optional[Tuple[float, float]] = None     # (p, vol_max)
+    eps: float = 1e-6
+    norm: Optional[Tuple[float, float]] = None      # (mean, std) of the log power
+    fmask: Tuple[int, int] = (0, 0)
+    tmask: Tuple[int, int] = (0, 0)
+    fill: float = 0.0
+
+    def __post_init__(self):
+        s = object.__setattr__
+        for k in ('n_fft', 'hop', 'shift'):
+            s(self, k, int(getattr(self, k)))
+        s(self, 'fmask', _mask(self.fmask, 'fmask'))
+        s(self, 'tmask', _mask(self.tmask, 'tmask'))
+        s(self, 'fill', float(self.fill))
+        s(self, 'eps', float(self.eps))
+        s(self, 'gain', _fpair(self.gain, 'gain'))
+        s(self, 'noise', _fpair(self.noise, 'noise', '(p, vol_max)'))
+        s(self, 'norm', _fpair(self.norm, 'norm', '(mean, std)'))
+        if self.n_fft % 2 or not 16 <= self.n_fft <= 512:
+            raise ValueError('WaveRecipe: n_fft is even, 16..512, got %d' % self.n_fft)
+        if not 1 <= self.hop <= self.n_fft:
+            raise ValueError('WaveRecipe: hop is 1..n_fft, got %d' % self.hop)
+        if self.shift < 0:
+            raise ValueError('WaveRecipe: shift is >= 0, got %d' % self.shift)
+        if self.gain is not None and self.gain[0] > self.gain[1]:
+            raise ValueError('WaveRecipe: gain is (lo, hi), lo <= hi, got %r' % (self.gain,))
+        if self.noise is not None and not (0 <= self.noise[0] <= 1 and self.noise[1] >= 0):
+            raise ValueError('WaveRecipe: noise is (p, vol_max), 0 <= p <= 1, vol_max >= 0, '
+                             'got %r' % (self.noise,))
+        if not (self.eps > 0 and math.isfinite(self.eps)):
+            raise ValueError('WaveRecipe: eps is > 0, got %r' % self.eps)
+        if self.norm is not None and not self.norm[1] > 0:
+            raise ValueError('WaveRecipe: norm is (mean, std), std > 0, got %r' % (self.norm,))
+        if not math.isfinite(self.fill):
+            raise ValueError('WaveRecipe: fill is finite, got %r' % self.fill)
+
+    @classmethod
+    def parse(cls, spec):
+        """``wave:nfft=200,hop=100,shift=1600,gain=0.8:1.2,noise=0.8x0.1,eps=1e-6,norm=-5:4,
+        fmask=2x10,tmask=2x20,fill=0`` (the ``wave:`` prefix is optional here)."""
+        spec = spec.strip()
+        if spec.startswith('wave:'):
+            spec = spec[5:]
+        kw = {}
+        for item in (spec.split(',') if spec else []):
+            if '=' not in item:
+                raise ValueError('WaveRecipe.parse: %r is not name=value' % item)
+            k, v = (s.strip() for s in item.split('=', 1))
+            if k in ('nfft', 'hop', 'shift'):
+                kw['n_fft' if k == 'nfft' else k] = int(v)
+            elif k in ('fmask', 'tmask', 'noise'):
+                nm = v.split('x')
+                if k == 'noise' and v in ('', 'none'):
+                    kw[k] = None
+                elif len(nm) != 2:
+                    raise ValueError('WaveRecipe.parse: %s is AxB, got %r' % (k, v))
+                else:
+                    kw[k] = (float(nm[0]), float(nm[1])) if k == 'noise' else \
+                        (int(nm[0]), int(nm[1]))
+            elif k in ('gain', 'norm'):
+                g = v.split(':')
+                if v in ('', 'none'):
+                    kw[k] = None
+                elif len(g) != 2:
+                    raise ValueError('WaveRecipe.parse: %s is A:B, got %r' % (k, v))
+                else:
+                    kw[k] = (float(g[0]), float(g[1]))
+            elif k in ('fill', 'eps'):
+                kw[k] = float(v)
+            else:
+                raise ValueError('WaveRecipe.parse: unknown key %r' % k)
+        return cls(**kw)
+
+    def spec(self):
+        """The ``parse`` form of this recipe, with the ``wave:`` prefix."""
+        out = ['nfft=%d' % self.n_fft, 'hop=%d' % self.hop, 'shift=%d' % self.shift]
+        if self.gain is not None:
+            out.append('gain=%r:%r' % self.gain)
+        if self.noise is not None:
+            out.append('noise=%rx%r' % self.noise)
+        out.append('eps=%r' % self.eps)
+        if self.norm is not None:
+            out.append('norm=%r:%r' % self.norm)
+        out += ['fmask=%dx%d' % self.fmask, 'tmask=%dx%d' % self.tmask, 'fill=%r' % self.fill]
+        return 'wave:' + ','.join(out)
+
+    @property
+    def identity(self):
+        """No augmentation on: every draw is the identity whatever the random words."""
+        return (self.shift == 0 and self.gain is None and self.noise is None
+                and 0 in self.fmask and 0 in self.tmask)
+
+    def out_hw(self, L):
+        """(F, T): bins and frames of an L-sample clip, the network's input size."""
+        return self.n_fft // 2 + 1, 1 + L // self.hop
+
+    def affine(self):
+        """(a, b) of ``y = a ln(power + eps) + b``."""
+        return (1.0, 0.0) if self.norm is None else (1.0 / self.norm[1],
+                                                     -self.norm[0] / self.norm[1])
+
+    def check(self, L, noise_shape=None):
+        """Raise unless the recipe fits L-sample clips and a noise bank of shape (Nn, Ln)
+        (``None``: no bank); names the field that does not."""
+        if L <= self.n_fft // 2:
+            raise ValueError('WaveRecipe: n_fft %d needs clips longer than n_fft/2, got L = %d'
+                             % (self.n_fft, L))
+        F, T = self.out_hw(L)
+        if self.fmask[1] > F:
+            raise ValueError('WaveRecipe: fmask width %d exceeds F = %d' % (self.fmask[1], F))
+        if self.tmask[1] > T:
+            raise ValueError('WaveRecipe: tmask width %d exceeds T = %d' % (self.tmask[1], T))
+        if self.noise is not None and noise_shape is None:
+            raise ValueError('WaveRecipe: noise=%r needs a noise bank [Nn][Ln]' % (self.noise,))
+        if noise_shape is not None and (len(noise_shape) != 2 or noise_shape[0] < 1
+                                        or noise_shape[1] < L):
+            raise ValueError('WaveRecipe: noise bank must be [Nn >= 1][Ln >= L = %d], got %s'
+                             % (L, tuple(noise_shape)))
+
+    def draw(self, L, noise_shape=None, generator=None):
+        """One slot's draws from torch's RNG, in the kernel's ranges and ``params`` layout."""
+        self.check(L, noise_shape)
+
+        def ri(n):
+            return int(torch.randint(0, n, (1,), generator=generator).item())
+
+        def ru():
+            return float(torch.rand(1, generator=generator).item())
+        p = [0.0] * WAVE_PARAMS
+        p[0] = float(ri(2 * self.shift + 1) - self.shift)
+        p[1] = 1.0
+        if self.gain is not None:
+            p[1] = self.gain[0] + (self.gain[1] - self.gain[0]) * ru()
+        if self.noise is not None and ru() < self.noise[0]:
+            p[2:6] = [1.0, float(ri(noise_shape[0])), float(ri(noise_shape[1] - L + 1)),
+                      self.noise[1] * ru()]
+        F, T = self.out_hw(L)
+        for base, (n, mx), size in ((6, self.fmask, F), (10, self.tmask, T)):
+            for k in range(n):
+                w = ri(mx + 1)
+                p[base + 2 * k], p[base + 2 * k + 1] = float(ri(size - w + 1)), float(w)
+        return p
+
+    def identity_params(self):
+        p = [0.0] * WAVE_PARAMS
+        p[1] = 1.0
+        return p
+
+    def table(self, ksteps=None):
+        """The window-folded DFT table of the kernel, fp64 -> fp32 [4*ksteps][2*F16]: columns
+        ``[0, F)`` hold ``w[n] cos(2 pi k n / W)``, columns ``[F16, F16 + F)`` hold
+        ``-w[n] sin(2 pi k n / W)``; rows ``>= W`` and the padding columns are zero."""
+        W, F = self.n_fft, self.n_fft // 2 + 1
+        F16 = (F + 15) // 16 * 16
+        rows = 4 * ksteps if ksteps else W
+        n = torch.arange(W, dtype=torch.float64).view(W, 1)
+        k = torch.arange(F, dtype=torch.float64).view(1, F)
+        w = 0.5 - 0.5 * torch.cos(2 * math.pi * n / W)
+        ang = 2 * math.pi * ((n * k) % W) / W
+        tab = torch.zeros(rows, 2 * F16, dtype=torch.float64)
+        tab[:W, :F] = w * torch.cos(ang)
+        tab[:W, F16:F16 + F] = -w * torch.sin(ang)
+        return tab.to(torch.float32)
+
+    # ---------------------------------------------------------------- CPU reference
+    def reference(self, x, noise, params, dtype=torch.bfloat16):
+        """The recipe on one clip ``x[L]`` (int16 or float) with explicit draws ``params``
+        (``WAVE_PARAMS`` values, the kernel's layout) and the noise bank ``noise`` ([Nn][Ln] or
+        None) -> [F][T][8] ``dtype``, the pool's layout.  fp64 from step 1 on, then one rounding
+        to ``dtype``."""
+        def f64(t):
+            t = torch.as_tensor(t)
+            return t.double() / 32768 if t.dtype == torch.int16 else t.double()
+        x = torch.as_tensor(x)
+        if x.dim() != 1:
+            raise ValueError('reference: the clip must be [L]')
+        L, W, hop = x.shape[0], self.n_fft, self.hop
+        self.check(L, None if noise is None else tuple(noise.shape))
+        p = [float(v) for v in params]
+        if len(p) != WAVE_PARAMS:
+            raise ValueError('reference: params has %d values' % WAVE_PARAMS)
+        s = int(p[0])
+        j = torch.arange(L)
+        xs = f64(x)
+        xa = p[1] * torch.where((j - s >= 0) & (j - s < L), xs[(j - s).clamp(0, L - 1)],
+                                torch.zeros((), dtype=torch.float64))
+        if int(p[2]):
+            if noise is None:
+                raise ValueError('reference: params has noise on but there is no bank')
+            clip, off = int(p[3]), int(p[4])
+            xa = xa + p[5] * f64(noise[clip, off:off + L])
+        h = W // 2
+        xp = torch.cat([xa[1:h + 1].flip(0), xa, xa[L - h - 1:L - 1].flip(0)])
+        F, T = self.out_hw(L)
+        n = torch.arange(W, dtype=torch.float64).view(W, 1)
+        k = torch.arange(F, dtype=torch.float64).view(1, F)
+        w = 0.5 - 0.5 * torch.cos(2 * math.pi * n / W)
+        ang = 2 * math.pi * ((n * k) % W) / W
+        frames = xp.unfold(0, W, hop)[:T]                               # [T][W]
+        re, im = frames @ (w * torch.cos(ang)), frames @ (-w * torch.sin(ang))
+        a, b = self.affine()
+        y = (a * torch.log(re * re + im * im + self.eps) + b).t()       # [F][T]
+        f = torch.arange(F).view(F, 1)
+        t = torch.arange(T).view(1, T)
+        masked = torch.zeros(F, T, dtype=torch.bool)
+        for q in (6, 8):
+            masked |= (f >= int(p[q])) & (f < int(p[q]) + int(p[q + 1]))
+        for q in (10, 12):
+            masked |= (t >= int(p[q])) & (t < int(p[q]) + int(p[q + 1]))
+        y = torch.where(masked, torch.tensor(self.fill, dtype=torch.float64), y)
+        out = torch.zeros(F, T, 8, dtype=dtype)
+        out[:, :, 0] = y.to(dtype)
         return out

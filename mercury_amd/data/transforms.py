@@ -18,7 +18,9 @@ recipe (``Config.augment = 'dataset'``), so the native engine applies what the
 dataset's transform says; the kernel keeps values in float between the stages,
 where ``Resize`` and ``RandomAffine`` here round to uint8 (at most one level apart).
 ``SpecAugment`` is the float-spectrogram counterpart: it carries a ``SpecRecipe`` that the
-pool build runs from a planar bf16 shard (``pool_spec_kernel``).
+pool build runs from a planar bf16 shard (``pool_spec_kernel``).  ``WaveSpectrogram`` is the
+raw-waveform one: its ``WaveRecipe`` augments the clip and makes the log-spectrogram, which the
+pool build runs from an int16 / float32 shard of clips (``pool_wave_kernel``).
 """
 from __future__ import annotations
 
@@ -289,6 +291,39 @@ class SpecAugment(object):
 
     def __repr__(self):
         return 'SpecAugment(%r)' % self.recipe.spec()
+
+
+class WaveSpectrogram(object):
+    """A ``WaveRecipe`` (``data/augment.py``: shift, gain and background noise on the raw clip,
+    then the log-spectrogram) on one waveform [L] (int16 PCM or float) -> float32 [1][F][T].
+    The draws come from torch's RNG (``generator``) through ``WaveRecipe.draw``, the arithmetic
+    is ``WaveRecipe.reference``; ``noise`` is the bank [Nn][Ln] a ``noise=`` recipe mixes from,
+    ``augment=False`` the evaluation transform (identity draws).  The eager ``Trainer`` runs it
+    as the dataset's transform on any device; ``Config(augment='dataset')`` hands its recipe to
+    the native engine's pool build (``pool_wave_kernel``) instead."""
+
+    def __init__(self, recipe, noise=None, generator=None, augment=True):
+        from .augment import WaveRecipe
+        self.recipe = WaveRecipe.parse(recipe) if isinstance(recipe, str) else recipe
+        if not isinstance(self.recipe, WaveRecipe):
+            raise ValueError('WaveSpectrogram: expected a WaveRecipe or its spec string, got %r'
+                             % (recipe,))
+        self.noise = None if noise is None else torch.as_tensor(noise)
+        self.generator, self.augment = generator, augment
+        self.last = None                 # the last call's draws (WaveRecipe's params layout)
+
+    def __call__(self, x):
+        x = torch.as_tensor(x)
+        if self.augment:
+            shape = None if self.noise is None else tuple(self.noise.shape)
+            self.last = self.recipe.draw(x.shape[0], shape, self.generator)
+        else:
+            self.last = self.recipe.identity_params()
+        y = self.recipe.reference(x, self.noise, self.last, dtype=torch.float32)
+        return y[:, :, 0].unsqueeze(0).contiguous()
+
+    def __repr__(self):
+        return 'WaveSpectrogram(%r)' % self.recipe.spec()
 
 
 def cifar_train_transform():

@@ -33,7 +33,7 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
-from ..data.augment import PHOTO_PARAMS, SPEC_PARAMS, SpecRecipe
+from ..data.augment import PHOTO_PARAMS, SPEC_PARAMS, WAVE_PARAMS, SpecRecipe, WaveRecipe
 from ..ops import hconv, tune
 from ..ops.conv import cpad8, slab_bytes
 from ..parallel.buckets import default_bucket_bytes
@@ -166,8 +166,13 @@ class NativeEngine(object):
         self.eval_augment = self._recipe(eval_augment)
         if isinstance(self.eval_augment, SpecRecipe):
             raise ValueError('eval_augment: a SpecRecipe augments training pools only')
+        if isinstance(self.eval_augment, WaveRecipe):
+            raise ValueError('eval_augment: a WaveRecipe goes in augment; evaluation runs it '
+                             'with the identity draws')
         self.aug_params = None           # [P][8] fp32: the last pool's draws (set_shard);
         #                                  [P][12] for a SpecRecipe, [P][16] with rrc / jitter
+        #                                  and for a WaveRecipe
+        self.noise = None                # [Nn][Ln] background clips of a WaveRecipe (set_shard)
         self.seed = seed
         self.alpha, self.ema_alpha, self.importance = alpha, ema_alpha, importance
         self.world_size = world_size
@@ -819,6 +824,11 @@ class NativeEngine(object):
         if isinstance(recipe, SpecRecipe):
             recipe.check(self.lw.in_channels, self.H, self.W)
             return recipe
+        if isinstance(recipe, WaveRecipe):       # (checked against the clips in _device_inputs)
+            if self.lw.in_channels != 1:
+                raise ValueError('a WaveRecipe makes one-channel inputs, the network takes %d'
+                                 % self.lw.in_channels)
+            return recipe
         recipe = recipe.with_crop((self.H, self.W))
         if recipe.out_hw != (self.H, self.W):
             raise ValueError('augmentation recipe crops to %s but the engine was built for '
@@ -832,6 +842,18 @@ class NativeEngine(object):
         as bf16 [N][C][H][W] (the same rounding, one eighth of the bytes at C = 1)."""
         x = torch.as_tensor(np.ascontiguousarray(images)) if not torch.is_tensor(images) \
             else images
+        if isinstance(recipe, WaveRecipe):
+            if x.dim() != 2 or x.dtype not in (torch.int16, torch.float32):
+                raise ValueError('a WaveRecipe needs an int16 or float32 shard [N][L], got %s %s'
+                                 % (x.dtype, tuple(x.shape)))
+            recipe.check(x.shape[1], None if self.noise is None else tuple(self.noise.shape))
+            if recipe.out_hw(x.shape[1]) != (self.H, self.W):
+                raise ValueError('the WaveRecipe makes %dx%d spectrograms of %d-sample clips but '
+                                 'the engine was built for image_hw=%s'
+                                 % (*recipe.out_hw(x.shape[1]), x.shape[1], (self.H, self.W)))
+            return x.to(self.device).contiguous()      # the shard stays in its own dtype
+        if x.dim() == 2:
+            raise ValueError('a waveform shard [N][L] needs a WaveRecipe (augment=\'wave:...\')')
         if isinstance(recipe, SpecRecipe):
             C = self.lw.in_channels
             if x.dtype == torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (C, self.H, self.W):
@@ -864,14 +886,27 @@ class NativeEngine(object):
             ops.nchw_to_nhwc8(blk, out[s0:s0 + step])
         return out
 
-    def set_shard(self, images, labels):
+    def set_shard(self, images, labels, noise=None):
         """Keep this rank's training shard resident in HBM: uint8 [Ns][H][W][3] images, or
-        float [Ns][C][H][W] inputs pre-converted to NHWC bf16 (planar bf16 under a SpecRecipe)."""
+        float [Ns][C][H][W] inputs pre-converted to NHWC bf16 (planar bf16 under a SpecRecipe),
+        or -- under a WaveRecipe -- raw clips [Ns][L], int16 or float32, in their own dtype,
+        with the ``noise`` bank [Nn][Ln] of the same dtype a ``noise=`` recipe mixes from."""
+        if noise is not None:
+            if not isinstance(self.augment, WaveRecipe):
+                raise ValueError('noise: a noise bank belongs to a WaveRecipe')
+            nz = torch.as_tensor(np.ascontiguousarray(noise)) if not torch.is_tensor(noise) \
+                else noise
+            self.noise = nz.to(self.device).contiguous()
         x = self._device_inputs(images, self.augment)
         if x.shape[0] < 1:
             raise ValueError('empty shard')
+        if self.noise is not None and self.noise.dtype != x.dtype:
+            raise ValueError('noise bank is %s but the shard is %s' % (self.noise.dtype, x.dtype))
+        if isinstance(self.augment, WaveRecipe):     # the DFT table, before any graph capture
+            ops.importance.pool_wave_table(self.augment, self.device)
         if self.augment is not None and self.aug_params is None:
             n = SPEC_PARAMS if isinstance(self.augment, SpecRecipe) else \
+                WAVE_PARAMS if isinstance(self.augment, WaveRecipe) else \
                 PHOTO_PARAMS if self.augment.photo else 8
             self.aug_params = torch.zeros(self.P, n, dtype=torch.float32, device=self.device)
         # (a shard smaller than one batch -- possible for a Dirichlet non-IID split at large
@@ -927,7 +962,7 @@ class NativeEngine(object):
             # (epoch-shuffled, augmented), no pool forward, unit weights
             ops.pool_build(self.shard, self.shard_labels, self.ctrl, sm.input, sm.label,
                            sm.index, self.B, self.B, self.seed, recipe=self.augment,
-                           params=self.aug_params)
+                           params=self.aug_params, noise=self.noise)
             self.ctrl[0:1].add_(1)
             self.idx.copy_(self._arange_b)
             self.isw.fill_(1.0)
@@ -941,7 +976,7 @@ class NativeEngine(object):
         ops.pool_build(self.shard, self.shard_labels, self.ctrl, sm.input, sm.label, sm.index,
                        self.P, self.B, self.seed, zero=sm.stats_arena,
                        shuffle=self.sampler != 'groupwise', recipe=self.augment,
-                       params=self.aug_params)
+                       params=self.aug_params, noise=self.noise)
         # (the scoring convs keep their full occupancy: reserving extra LDS per scoring block
         # so train blocks fit beside them measured 1.70-2.21 ms/step vs 1.65 -- in the
         # concurrent step the GPU is throughput-bound, bench/ab_env.sh)
@@ -1494,8 +1529,13 @@ class NativeEngine(object):
         """Eval-mode (running-stats BN) loss / accuracy over uint8 HWC images (or float NCHW
         inputs) on device.  ``augment`` (default: the engine's ``eval_augment``): the recipe
         applied to the images, its random crop included -- drawn from the engine's seed and the
-        batch number, so a second call sees the same views; the batch order is kept."""
+        batch number, so a second call sees the same views; the batch order is kept.
+        Raw clips [N][L] take the engine's WaveRecipe by default and run it with the identity
+        draws (``pool_wave_kernel``, ``augment=False``)."""
         recipe = self._recipe(augment) if augment is not None else self.eval_augment
+        if recipe is None and isinstance(self.augment, WaveRecipe) and np.ndim(images) == 2:
+            recipe = self.augment
+        wave = isinstance(recipe, WaveRecipe)
         imgs = self._device_inputs(images, recipe)
         labs = torch.as_tensor(np.asarray(labels), dtype=torch.int64).to(self.device)
         n = imgs.shape[0]
@@ -1509,7 +1549,11 @@ class NativeEngine(object):
         while done < n:
             b = min(batch, n - done)
             m = self.mode('eval%d' % b, b, 0, False)
-            if recipe is not None:
+            if wave:
+                ops.pool_build(imgs[done:done + b], labs[done:done + b], ctrl, m.input, m.label,
+                               m.index, b, b, self.seed, augment=False, shuffle=False,
+                               recipe=recipe, noise=self.noise)
+            elif recipe is not None:
                 ops.pool_build(imgs[done:done + b], labs[done:done + b], ctrl, m.input, m.label,
                                m.index, b, b, self.seed, shuffle=False, recipe=recipe)
                 ctrl[0:1].add_(1)       # (the next batch draws its own crops)
@@ -1518,12 +1562,12 @@ class NativeEngine(object):
                                m.index, b, b, self.seed, augment=False, shuffle=False)
             x = self.forward(m)
             self.head(m, x, 'eval', meters=self.eval_meters)
-            if recipe is not None:
+            if recipe is not None and not wave:
                 loss_sum += m.losses[:b].double().sum()
             done += b
         r = self.eval_meters[:6].tolist()
         self.eval_topk = (int(r[5]), int(r[1]))
-        if recipe is not None:
+        if recipe is not None and not wave:
             r[0] = loss_sum.item()
         return r[0] / max(r[1], 1), r[2] / max(r[1], 1), int(r[1])
 
@@ -1557,6 +1601,9 @@ def _dataset_arrays(loader):
 
 def _image_hw(x):
     """uint8 [N][H][W][3] images or float [N][C][H][W] inputs -> (H, W)."""
+    if x.ndim == 2:
+        raise ValueError('a dataset of raw clips [N][L] needs a wave recipe '
+                         "(Config.augment = 'wave:...' or a WaveSpectrogram transform)")
     return tuple(x.shape[1:3]) if x.dtype == np.uint8 else tuple(x.shape[2:4])
 
 
@@ -1566,18 +1613,22 @@ def _config_recipes(cfg, presam_loader, test_loader):
     is an ``AugmentRecipe.parse`` spec, evaluated with its Resize, crop (``rrc`` included: there
     is no CenterCrop) and Normalize only.
     A spec starting with ``spec:`` (``SpecRecipe.parse``), or a ``transforms.SpecAugment`` as
-    the train dataset's transform, gives that spectrogram recipe and no eval recipe."""
+    the train dataset's transform, gives that spectrogram recipe and no eval recipe; so does a
+    spec starting with ``wave:`` (``WaveRecipe.parse``) or a ``transforms.WaveSpectrogram``, for
+    a dataset of raw clips [N][L] (evaluation runs the same recipe with the identity draws)."""
     from ..data.augment import AugmentRecipe
-    from ..data.transforms import SpecAugment
+    from ..data.transforms import SpecAugment, WaveSpectrogram
     spec = getattr(cfg, 'augment', 'cifar')
     if spec == 'cifar':
         return None, None
     if spec.startswith('spec:'):
         return SpecRecipe.parse(spec), None
+    if spec.startswith('wave:'):
+        return WaveRecipe.parse(spec), None
     if spec == 'dataset':
         tr = [getattr(getattr(ld, 'dataset', None), 'transform', None)
               for ld in (presam_loader, test_loader)]
-        if isinstance(tr[0], SpecAugment):
+        if isinstance(tr[0], (SpecAugment, WaveSpectrogram)):
             return tr[0].recipe, None
         return AugmentRecipe.from_transform(tr[0]), AugmentRecipe.from_transform(tr[1])
     aug = AugmentRecipe.parse(spec)
@@ -1619,8 +1670,14 @@ class NativeTrainer(Trainer):
         osp = ops.optimizer_spec(optimizer)       # raises on anything the kernel cannot run
         x, y = _dataset_arrays(presam_loader)
         aug, eval_aug = _config_recipes(cfg, presam_loader, test_loader)
-        image_hw = _image_hw(x)
-        if aug is not None and not isinstance(aug, SpecRecipe):
+        if isinstance(aug, WaveRecipe):
+            if x.ndim != 2:
+                raise ValueError('a wave recipe needs a dataset of raw clips [N][L], got %s'
+                                 % (x.shape,))
+            image_hw = aug.out_hw(x.shape[1])
+        else:
+            image_hw = _image_hw(x)
+        if aug is not None and not isinstance(aug, (SpecRecipe, WaveRecipe)):
             image_hw = aug.with_crop(image_hw).out_hw
         self.engine = NativeEngine(
             net, self.device, self.batch_size, cfg.presample_batches, image_hw=image_hw,
@@ -1637,7 +1694,18 @@ class NativeTrainer(Trainer):
             force_buckets=cfg.force_buckets, clip_grad_norm=cfg.clip_grad_norm,
             label_smoothing=cfg.label_smoothing, topk=cfg.topk)
         self.label_smoothing, self.topk = self.engine.label_smoothing, self.engine.topk
-        self.engine.set_shard(x, y)
+        if isinstance(aug, WaveRecipe):
+            try:
+                ds = presam_loader.dataset       # the bank: the dataset's, else its transform's
+                bank = getattr(ds, 'noise', None)
+                if bank is None:
+                    bank = getattr(getattr(ds, 'transform', None), 'noise', None)
+                self.engine.set_shard(x, y, noise=bank)
+            except ValueError:
+                self.engine.close()
+                raise
+        else:
+            self.engine.set_shard(x, y)
         self.engine.roctx = cfg.roctx
         from ..utils.profiling import StepWindow
         self.profile_window = StepWindow(cfg.profile_start, cfg.profile_steps)

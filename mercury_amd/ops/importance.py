@@ -4,13 +4,13 @@ from __future__ import annotations
 import torch
 
 from . import _chk, lib, ptr, stream_ptr
-from ..data.augment import PHOTO_PARAMS, SPEC_PARAMS, SpecRecipe
+from ..data.augment import PHOTO_PARAMS, SPEC_PARAMS, WAVE_PARAMS, SpecRecipe, WaveRecipe
 from ..data.transforms import CIFAR_MEAN, CIFAR_STD
 
 
 def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, pad=4,
                flip=True, augment=True, mean=CIFAR_MEAN, std=CIFAR_STD, shuffle=True, zero=None,
-               recipe=None, params=None, force_augment_kernel=False):
+               recipe=None, params=None, force_augment_kernel=False, noise=None):
     """Build a P-sample presample pool on device from either the uint8 image shard
     [Ns][H][W][3] (crop/flip/normalise on the fly) or a pre-converted bf16 shard
     [Ns][H][W][8] (non-image inputs: plain gather, no augmentation).  ``zero``: an fp32
@@ -29,8 +29,25 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
     shard [Ns][C][H][W], C <= 8, and a 4-d pool [P][H][W][8] (``pool_spec_kernel``); ``params``
     is then fp32 [P][12] (shift, gain, f0a, fwa, f0b, fwb, t0a, twa, t0b, twb, 0, 0).  With
     ``augment=False``, or ``SpecRecipe()``, the pool has the bits of the plain gather from the
-    same samples' NHWC8 shard."""
+    same samples' NHWC8 shard.
+
+    A ``data.augment.WaveRecipe`` (shift, gain, background noise on the waveform, then the
+    log-spectrogram) takes an int16 or float32 shard of raw clips [Ns][L], an optional ``noise``
+    bank [Nn][Ln] of the same dtype and a pool [P][n_fft/2+1][1+L//hop][8]
+    (``pool_wave_kernel``); ``params`` is then fp32 [P][16] (``data.augment.WAVE_PARAMS``).
+    ``augment=False`` draws the identity and still transforms.  The first build for an
+    ``(n_fft, device)`` makes the DFT table (an allocation and a copy): inside a graph capture
+    only after such a call or ``pool_wave_table`` (``NativeEngine.set_shard`` makes it)."""
     _chk(labels, torch.int64, 'labels')
+    if isinstance(recipe, WaveRecipe):
+        if force_augment_kernel:
+            raise ValueError('force_augment_kernel belongs to an AugmentRecipe')
+        return _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batch,
+                          seed, augment, shuffle, zero, recipe, params)
+    if noise is not None:
+        raise ValueError('noise: a noise bank belongs to a WaveRecipe')
+    if shard.dim() == 2:
+        raise ValueError('shard is [Ns][L] raw clips: that needs a WaveRecipe')
     if isinstance(recipe, SpecRecipe):
         if force_augment_kernel:
             raise ValueError('force_augment_kernel belongs to an AugmentRecipe')
@@ -122,6 +139,54 @@ def _pool_spec(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
                     zero.numel() if zero is not None else 0, recipe.shift, recipe.fmask[0],
                     recipe.fmask[1], recipe.tmask[0], recipe.tmask[1], lo, hi, recipe.fill,
                     ptr(params), chunks)
+
+
+_WAVE_TABLES = {}    # (n_fft, device) -> the DFT table, built once (never inside a capture)
+
+
+def pool_wave_table(recipe, device):
+    """``WaveRecipe.table`` padded to the kernel's K steps, resident on ``device``."""
+    key = (recipe.n_fft, str(device))
+    if key not in _WAVE_TABLES:
+        _WAVE_TABLES[key] = recipe.table(lib().pool_wave_ksteps(recipe.n_fft)).to(device)
+    return _WAVE_TABLES[key]
+
+
+def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, augment,
+               shuffle, zero, recipe, params, chunks=0):
+    if shard.dtype not in (torch.int16, torch.float32) or shard.dim() != 2:
+        raise ValueError('a WaveRecipe needs an int16 or float32 shard [Ns][L], got %s %s'
+                         % (shard.dtype, tuple(shard.shape)))
+    _chk(shard, shard.dtype, 'shard')
+    Ns, L = int(shard.shape[0]), int(shard.shape[1])
+    recipe.check(L, None if noise is None else tuple(noise.shape))
+    if noise is not None:
+        if noise.dtype != shard.dtype:
+            raise ValueError('noise bank is %s but the shard is %s' % (noise.dtype, shard.dtype))
+        _chk(noise, shard.dtype, 'noise')
+    F, T = recipe.out_hw(L)
+    if pool.dim() != 4 or tuple(pool.shape[1:]) != (F, T, 8):
+        raise ValueError('pool must be [P][%d][%d][8] for this WaveRecipe, got %s'
+                         % (F, T, tuple(pool.shape)))
+    _chk(pool, torch.bfloat16, 'pool', P * F * T * 8)
+    if params is not None:
+        _chk(params, torch.float32, 'params', P * WAVE_PARAMS)
+    tab = pool_wave_table(recipe, shard.device)
+    glo, ghi = recipe.gain or (1.0, 1.0)
+    p, vol = recipe.noise or (0.0, 0.0)
+    a, b = recipe.affine()
+    lib().pool_wave(shard=ptr(shard), noise=ptr(noise), tab=ptr(tab), tab_floats=tab.numel(),
+                    labels=ptr(labels), ctrl=ptr(ctrl), pool=ptr(pool), pool_label=ptr(pool_label),
+                    pool_index=ptr(pool_index), params=ptr(params), zero=ptr(zero),
+                    nzero=zero.numel() if zero is not None else 0, stream=stream_ptr(),
+                    f32=int(shard.dtype == torch.float32), Ns=Ns, L=L,
+                    Nn=noise.shape[0] if noise is not None else 0,
+                    Ln=noise.shape[1] if noise is not None else 0, n_fft=recipe.n_fft,
+                    hop=recipe.hop, P=P, batch=batch, augment=int(augment), shuffle=int(shuffle),
+                    seed=int(seed) & 0xffffffff, shift=recipe.shift, gain_lo=glo, gain_hi=ghi,
+                    noise_p=p, vol_max=vol, eps=recipe.eps, log_a=a, log_b=b,
+                    fmask_n=recipe.fmask[0], fmask_max=recipe.fmask[1], tmask_n=recipe.tmask[0],
+                    tmask_max=recipe.tmask[1], fill=recipe.fill, chunks=chunks)
 
 
 def is_sample(losses, ema, ctrl, idx, w, P, B, group, alpha=0.5, ema_alpha=0.9, seed=0,
