@@ -1,4 +1,5 @@
-"""Cost of the waveform front end (csrc/pool_wave.hip pool_wave_kernel).
+"""Cost of the waveform front end (csrc/pool_wave.hip pool_wave_kernel, csrc/pool_mel.hip
+pool_wave_mel_kernel).
 
     python bench/wave_bench.py pool [--out FILE] [--runs R] [--ns N]
     python bench/wave_bench.py step [--out FILE] [--steps K] [--warmup W] [--runs R] [--ns N]
@@ -8,7 +9,9 @@
 100, 16000-sample int16 clips) at P = 320 and P = 32 (batch 32): ``pool_wave_kernel`` as the
 identity, with shift + gain, and as the full recipe, with the launcher's own frame chunks and with
 fixed numbers of them, beside ``pool_spec_kernel``'s identity on the same-sized planar bf16
-spectrogram shard.  Every call advances the pool counter.  Interleaved, ``--runs`` times.
+spectrogram shard; then ``pool_wave_mel_kernel`` as the identity with ``mel=80`` (80 x 161 log-mel
+pools) and ``mel=80,dct=13`` (13 x 161 MFCC pools), the first also with fixed chunk counts.  Every
+call advances the pool counter.  Interleaved, ``--runs`` times.
 
 ``step``: the vgg11-speech preset as ``bench.py`` builds it (a spectrogram shard, no recipe)
 against the same network fed from a synthetic int16 waveform shard through the full recipe,
@@ -16,7 +19,9 @@ ms/step, interleaved, ``--runs`` times.
 
 ``banks`` (no GPU): LDS bank conflicts of the A-operand read ``lds[(f0 + lane % 16) * hop + 4 k +
 lane / 16]`` for a few hops -- the worst number of lanes of a wave on one of the 64 banks, by
-the bank model of ``bench/lds_swizzle_check.py`` (``worst_b32``).
+the bank model of ``bench/lds_swizzle_check.py`` (``worst_b32``) -- and of the mel kernel's panel
+write ``(4 (lane / 16) + i) * pitch + lane % 16`` and read ``(lane % 16) * pitch + 4 k + lane / 16``
+for the pitches F16 + pad and M16 + pad it could take.
 One JSON line per measurement, appended to ``--out`` and printed.
 """
 from __future__ import annotations
@@ -71,7 +76,12 @@ def bench_pool(args):
     planar = torch.randn(min(Ns, 4096), 1, H, W, device=dev).bfloat16()
     labels = torch.randint(0, 30, (Ns,), device=dev)
     recipes = {'identity': WaveRecipe.parse('wave:nfft=200,hop=100,norm=-5:4'),
-               'shift+gain': WaveRecipe.parse(SHIFT_GAIN), 'full': WaveRecipe.parse(FULL)}
+               'shift+gain': WaveRecipe.parse(SHIFT_GAIN), 'full': WaveRecipe.parse(FULL),
+               'mel=80 identity': WaveRecipe.parse('wave:nfft=200,hop=100,norm=-5:4,mel=80'),
+               'mel=80,dct=13 identity':
+                   WaveRecipe.parse('wave:nfft=200,hop=100,norm=-5:4,mel=80,dct=13')}
+    kr = recipes['mel=80 identity'].mel_ksteps()
+    mel_macs = sum(4 * (hi - lo + 1) * 16 for lo, hi in zip(kr[::2], kr[1::2]))   # per frame
     for P in (320, 32):
         ctrl = torch.zeros(4, dtype=torch.int64, device=dev)
         pool = torch.zeros(P, H, W, 8, dtype=torch.bfloat16, device=dev)
@@ -79,8 +89,11 @@ def bench_pool(args):
         pi = torch.zeros(P, dtype=torch.int32, device=dev)
 
         def wave(recipe, chunks):
+            out = pool if not recipe.mel else torch.zeros(P, *recipe.out_hw(L), 8, device=dev,
+                                                          dtype=torch.bfloat16)
+
             def fn():
-                _pool_wave(shard, bank if recipe.noise else None, labels, ctrl, pool, pl, pi, P,
+                _pool_wave(shard, bank if recipe.noise else None, labels, ctrl, out, pl, pi, P,
                            B, 7, True, True, None, recipe, None, chunks=chunks)
                 ctrl[0:1].add_(1)
             return fn
@@ -95,8 +108,10 @@ def bench_pool(args):
 
         variants = [('pool_spec_kernel identity', 0, spec), ('counter increment alone', 0, tick)]
         for name, r in recipes.items():
-            for chunks in ((0, 2, 3, 4, 6, 11) if name == 'full' else (0,)):
-                variants.append(('pool_wave_kernel %s' % name, chunks, wave(r, chunks)))
+            sweep = {'full': (0, 2, 3, 4, 6, 11), 'mel=80 identity': (0, 3, 4, 6, 11)}
+            for chunks in sweep.get(name, (0,)):
+                variants.append(('pool_wave_%skernel %s' % ('mel_' if r.mel else '', name), chunks,
+                                 wave(r, chunks)))
         for run in range(args.runs):
             for label, chunks, fn in variants:
                 ctrl.zero_()
@@ -105,6 +120,9 @@ def bench_pool(args):
                        'chunks': chunks, 'us': round(us, 3)}
                 if 'wave' in label:     # the padded GEMM: 176 frames x 200 x (2 x 112) columns
                     rec['gflop'] = round(P * 2 * 176 * 200 * 2 * 112 / 1e9, 3)
+                if 'mel' in label:      # the K steps run per 16-band tile (+ 80 x 16 for dct)
+                    rec['gflop_mel'] = round(P * 2 * 176 * (mel_macs + (
+                        80 * 16 if 'dct' in label else 0)) / 1e9, 4)
                 emit(rec, args.out)
 
 
@@ -167,6 +185,15 @@ def bench_banks(args):
         worst = max(worst_b32(lambda lane: (lane % 16) * hop + 4 * k + lane // 16)
                     for k in range(4))
         emit({'bench': 'wave_banks', 'hop': hop, 'worst_lanes_per_bank': worst}, args.out)
+    for width in (112, 80, 48, 272, 128, 16):       # F16 or M16
+        for pad in (0, 1, 4, 8, 12):
+            pitch = width + pad
+            write = max(worst_b32(lambda lane: (4 * (lane // 16) + i) * pitch + lane % 16)
+                        for i in range(4))
+            read = max(worst_b32(lambda lane: (lane % 16) * pitch + 4 * k + lane // 16)
+                       for k in range(4))
+            emit({'bench': 'mel_panel_banks', 'pitch': pitch, 'pad': pad,
+                  'worst_lanes_per_bank_write': write, 'worst_lanes_per_bank_read': read}, args.out)
 
 
 def main():

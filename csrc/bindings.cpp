@@ -5,6 +5,7 @@
 // the HIP runtime -- no PyTorch headers -- and builds in seconds.  All shape,
 // dtype, device and contiguity validation happens in mercury_amd/ops/*.py, which
 // also fails loudly if this extension is missing on a GPU machine.
+#include <algorithm>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -779,7 +780,9 @@ PYBIND11_MODULE(_C, m) {
                         int Pn, int batch, int augment, int shuffle, uint32_t seed, int shift,
                         float gain_lo, float gain_hi, float noise_p, float vol_max, float eps,
                         float log_a, float log_b, int fmask_n, int fmask_max, int tmask_n,
-                        int tmask_max, float fill, int chunks) {
+                        int tmask_max, float fill, int chunks, int mel, int dct,
+                        uintptr_t mel_tab, long long mel_floats, uintptr_t dct_tab,
+                        long long dct_floats, std::vector<int> krange) {
     if (!std::isfinite(gain_lo) || !std::isfinite(gain_hi) || gain_hi < gain_lo ||
         !std::isfinite(fill) || !std::isfinite(log_a) || !std::isfinite(log_b) ||
         !(noise_p >= 0.f && noise_p <= 1.f) || !(vol_max >= 0.f) || !std::isfinite(vol_max))
@@ -787,14 +790,26 @@ PYBIND11_MODULE(_C, m) {
                                   "gain lo <= hi, noise p in [0, 1], vol_max >= 0");
     if (n_fft < 2 || hop < 1 || L < 1 || L >= (1 << 30) || shift < 0 || shift >= (1 << 30))
       throw std::invalid_argument("pool_wave: n_fft, hop, L positive; L and shift below 2^30");
+    if (krange.size() > 16)
+      throw std::invalid_argument("pool_wave: krange holds at most 8 (first, last) pairs");
     const int F = n_fft / 2 + 1;
-    PoolWaveArgs a{pool_build_args(shard, labels, ctrl, pool, pool_label, pool_index, Ns, F,
-                                   1 + L / hop, Pn, batch, 0, 0, augment, shuffle, seed,
+    PoolWaveArgs a{pool_build_args(shard, labels, ctrl, pool, pool_label, pool_index, Ns,
+                                   dct > 0 ? dct : mel > 0 ? mel : F, 1 + L / hop, Pn, batch, 0, 0, augment, shuffle, seed,
                                    {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, 0, zero, nzero),
                    P<const void>(noise), P<const float>(tab), tab_floats, f32, L, Nn, Ln, n_fft,
                    hop, (F + 15) & ~15, shift, gain_lo, gain_hi, noise_p, vol_max, eps, log_a,
                    log_b, fmask_n, fmask_max, tmask_n, tmask_max, fill, P<float>(params), chunks,
                    0, 0};
+    a.mel = mel;
+    a.dct = dct;
+    a.M16 = (mel + 15) & ~15;
+    a.C16 = (dct + 15) & ~15;
+    a.mel_tab = P<const float>(mel_tab);
+    a.mel_floats = mel_floats;
+    a.dct_tab = P<const float>(dct_tab);
+    a.dct_floats = dct_floats;
+    a.krange_n = (int)krange.size();
+    std::copy(krange.begin(), krange.end(), a.krange);
     pool_wave_launch(a, S(st));
     check_launch("pool_wave");
   }, py::kw_only(), py::arg("shard"), py::arg("noise") = 0, py::arg("tab"),
@@ -807,7 +822,9 @@ PYBIND11_MODULE(_C, m) {
      py::arg("noise_p") = 0.f, py::arg("vol_max") = 0.f, py::arg("eps"), py::arg("log_a") = 1.f,
      py::arg("log_b") = 0.f, py::arg("fmask_n") = 0, py::arg("fmask_max") = 0,
      py::arg("tmask_n") = 0, py::arg("tmask_max") = 0, py::arg("fill") = 0.f,
-     py::arg("chunks") = 0);
+     py::arg("chunks") = 0, py::arg("mel") = 0, py::arg("dct") = 0, py::arg("mel_tab") = 0,
+     py::arg("mel_floats") = 0, py::arg("dct_tab") = 0, py::arg("dct_floats") = 0,
+     py::arg("krange") = std::vector<int>());
   m.def("is_sample", [](uintptr_t losses, uintptr_t ema, uintptr_t ctrl, uintptr_t idx, uintptr_t w,
                         uintptr_t meters, int Pn, int B, int group, int importance, float alpha,
                         float ema_alpha, uint32_t seed, uintptr_t st, int alias, uintptr_t gl,

@@ -219,10 +219,25 @@ struct PoolWaveArgs {
                                  //   fwa, f0b, fwb, t0a, twa, t0b, twb, 0, 0
   int chunks;                    // frame chunks per slot (grid.y); 0: the launcher's measured rule
   int tiles_per_chunk, lds_words;   // (filled in by the launcher)
+  // log-mel / MFCC (pool_mel.hip, pool_wave_mel_kernel); mel = 0: off, b.H = F and the kernel
+  // above runs.  With mel on b.H = R = dct ? dct : mel rows; masks are drawn on (R, T).
+  int mel, dct;                  // mel bands M (0 or 8..128), cepstral coefficients C (0..M)
+  int M16, C16;                  // M and C rounded up to 16 (C16 = 0 without dct)
+  const float* mel_tab;          // [F16][M16] filter bank, zero padding rows and columns
+  long long mel_floats;
+  const float* dct_tab;          // [M16][C16] orthonormal DCT-II, rows >= M zero
+  long long dct_floats;
+  int krange[16];                // per 16-band tile: first, last 4-bin K step holding a nonzero
+  int krange_n;                  // values given: 2 * M16 / 16
+  int panel_pitch, lm_pitch;     // (launcher) LDS pitches of the power and log-mel panels, words
+  int panel_off;                 // (launcher) first LDS word of the power panel
 };
 // throws std::invalid_argument on a shape the kernel cannot run (never a substitute)
 void pool_wave_launch(const PoolWaveArgs& a, hipStream_t st);
 int pool_wave_ksteps(int n_fft);   // K steps (of 4 samples) the table is padded to; 0: unsupported
+// the mel / MFCC kernel behind pool_wave_launch (a.mel > 0): the shared checks are done, nk =
+// pool_wave_ksteps(n_fft); checks the new arguments and the LDS budget, then launches
+void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st);
 
 struct IsSampleArgs {
   const float* losses;           // [P]

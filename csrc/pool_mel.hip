@@ -1,0 +1,228 @@
+// Log-mel and MFCC pools from raw clips (WaveRecipe with mel > 0, mercury_amd/data/augment.py):
+// pool_wave.hip's front end with a mel filter bank, and optionally a DCT, between the power and
+// the store, all three GEMMs on v_mfma_f32_16x16x4_f32 in one launch.
+//
+// pool_wave_mel : shard [Ns][L] -> shift, gain, noise mix, reflect padding (pool_wave_slot.h) ->
+//                 windowed DFT -> p[t][k] = re^2 + im^2 -> mel[t][m] = sum_k p[t][k] fb[k][m] ->
+//                 lm = ln(mel + eps) -> [c[t][j] = sum_m lm[t][m] D[m][j]] -> a * . + b -> masks
+//                 -> bf16 channel 0 of the NHWC8 pool [P][R][T][8], R = dct ? dct : mel rows.
+//
+// Why a kernel of its own: in pool_wave_kernel a wave owns 16 bins for all frames, so nothing
+// crosses lanes after the DFT.  A mel band sums over bins, that is over waves, so the power goes
+// through LDS and the block is re-split for the second GEMM.
+//
+// Grid (slot, frame chunk), the chunk rule of pool_wave.hip with the panels added to the LDS need.
+// LDS, in fp32 words:
+//   [0, lds_words)                      the waveform stretch (phase 1's A operand); dead after
+//                                       phase 1, so the log-mel panel of phase 3 lies over it
+//   [panel_off, + 16 tiles * PP)        power panel [frame][bin], pitch PP = F16 + 4
+//   [0, 16 tiles * LP)  (DCT only)      log-mel panel [frame][band], pitch LP = M16 + 4
+// Pitch.  An accumulator lane (col = lane % 16, kq = lane / 16) holds frames 4 kq + i, i < 4, of
+// column col, so store i of a wave goes to word (r0 + 4 kq + i) * PP + c0 + col: bank
+// 4 kq PP + col + const (mod 64).  The next GEMM's A operand of K step k is the word
+// (r0 + col) * PP + 4 k + kq: bank col PP + kq + const.  With PP = 4 (mod 16), PP = 4 q, q odd:
+// 4 kq PP = 16 q kq runs over {0, 16, 32, 48} and col < 16 fills each quarter; col PP = 4 (q col
+// mod 16) runs over the 16 multiples of 4 and kq < 4 fills the gaps.  Both touch 64 distinct
+// banks.  F16 and M16 are multiples of 16, so + 4 is the smallest such pitch.
+//
+// Phase 1 (DFT) is pool_wave_kernel's table-stationary loop: a wave owns a 16-bin tile, holds
+// its 2 * NK table fragments in registers and walks the chunk's 16-frame tiles; each lane writes
+// re^2 + im^2 of its 4 frames into the power panel.  The padding bins (>= F) are written too:
+// their table columns are zero, so they are the exact zeros the mel GEMM's padding rows expect.
+// Phase 2 (mel) is [frames x F16] . [F16 x M16]: the waves take (frame tile, band tile) pairs
+// round-robin, A from the panel, B from mel_tab in global memory (at most 272 x 128 floats, L2).
+// The bank is banded: krange (kernel argument, checked by the launcher) gives each band tile's
+// first and last 4-bin K step with a nonzero, and the K loop runs only those; the skipped
+// products are exact zeros.  Without DCT the log, the affine, the masks and the 16-byte pixel
+// stores follow in registers (4 consecutive frames of one band: 64 contiguous bytes).
+// Phase 3 (DCT): ln(mel + eps) goes to the log-mel panel instead -- padding bands as ln(eps),
+// which dct_tab's zero rows >= M cancel -- and after a barrier [frames x M16] . [M16 x C16]
+// against dct_tab, then affine, masks, store.
+// No atomics, fixed K order: launches are bit-equal and capturable.
+#include <stdexcept>
+
+#include "common.h"
+#include "kernels.h"
+#include "pool_geom.h"
+#include "pool_wave_slot.h"
+
+namespace {
+
+constexpr int PANEL_PAD = 4;     // pitch = width + 4 = 4 (mod 16), see above
+
+// Frames tb..tb+3 of pool row `row`: y = log_a * v + log_b, fill where masked, one bf16 rounding
+// into channel 0 of the 16-byte pixel, channels 1..7 +0.
+MA_DEV void mel_store4(const PoolWaveArgs& a, const WaveSlot& s, int slot, int row, int tb,
+                       const float v[4]) {
+  const int T = a.b.W;
+  const bf16 fill = f2bf(a.fill), zero = f2bf(0.f);
+  const bool rmasked = (row >= s.f0[0] && row < s.f0[0] + s.fw[0]) ||
+                       (row >= s.f0[1] && row < s.f0[1] + s.fw[1]);
+  bf16* o = a.b.pool + (((size_t)slot * a.b.H + row) * T + tb) * 8;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int tt = tb + i;
+    if (tt >= T) break;
+    const bool masked = rmasked || (tt >= s.t0[0] && tt < s.t0[0] + s.tw[0]) ||
+                        (tt >= s.t0[1] && tt < s.t0[1] + s.tw[1]);
+    bf16x8 px;
+    px[0] = masked ? fill : f2bf(a.log_a * v[i] + a.log_b);
+#pragma unroll
+    for (int c = 1; c < 8; ++c) px[c] = zero;
+    *(bf16x8*)(o + (size_t)i * 8) = px;
+  }
+}
+
+// One 16 x 16 output tile of [rows x K] . [K x N]: A rows r0.. of an LDS panel of pitch lda, B
+// columns n0.. of a global table of pitch ldb, K steps k0..k1 (inclusive) of 4.
+MA_DEV f32x4 panel_gemm(const float* panel, int lda, int r0, const float* tab, int ldb, int n0,
+                        int k0, int k1, int col, int kq) {
+  const float* ap = panel + (r0 + col) * lda + kq;
+  const float* bp = tab + (size_t)kq * ldb + n0 + col;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (int k = k0; k <= k1; ++k)
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[4 * k], bp[(size_t)(4 * k) * ldb], acc, 0, 0, 0);
+  return acc;
+}
+
+template <typename S, int NK, bool DCT>
+__global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(PoolWaveArgs a) {
+  extern __shared__ float lds[];
+  const PoolBuildArgs& b = a.b;
+  const int slot = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+  const int T = b.W;
+  if (b.zero && blockIdx.y == 0)
+    for (int j = slot * nthr + tid; j < b.nzero; j += gridDim.x * nthr) b.zero[j] = 0.f;
+  int64_t gb;
+  int t;
+  const uint32_t src = pool_src(b, slot, gb, t);
+  const WaveSlot s = wave_slot_draws(a, gb, t);
+  if (tid == 0 && blockIdx.y == 0) wave_slot_header(a, slot, src, s);
+  const int ntiles = (T + 15) >> 4;
+  const int tile0 = blockIdx.y * a.tiles_per_chunk;
+  const int ntile = min(a.tiles_per_chunk, ntiles - tile0);
+  wave_stage<S>(a, s, src, tile0 * 16 * a.hop, lds, tid, nthr);
+  __syncthreads();
+
+  // ---- phase 1: DFT, table stationary, frames streaming; power into the panel
+  const int lane = tid & 63, nw = nthr >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int col = lane & 15, kq = lane >> 4;
+  const int ldt = 2 * a.F16, nbt = a.F16 >> 4, PP = a.panel_pitch;
+  float* panel = lds + a.panel_off;
+  for (int bt = wave; bt < nbt; bt += nw) {
+    float bc[NK], bs[NK];
+    const float* tp = a.tab + (size_t)kq * ldt + bt * 16 + col;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      bc[k] = tp[(size_t)(4 * k) * ldt];
+      bs[k] = tp[(size_t)(4 * k) * ldt + a.F16];
+    }
+    for (int ft = 0; ft < ntile; ++ft) {
+      const float* fp = lds + (ft * 16 + col) * a.hop + kq;
+      f32x4 re = {0.f, 0.f, 0.f, 0.f}, im = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < NK; ++k) {
+        const float av = fp[4 * k];
+        re = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bc[k], re, 0, 0, 0);
+        im = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bs[k], im, 0, 0, 0);
+      }
+      float* pw = panel + (ft * 16 + kq * 4) * PP + bt * 16 + col;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pw[i * PP] = re[i] * re[i] + im[i] * im[i];
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 2: mel bands, (frame tile, band tile) pairs round-robin over the waves
+  const int nmt = a.M16 >> 4, LP = a.lm_pitch;
+  for (int p = wave; p < nmt * ntile; p += nw) {
+    const int ft = p / nmt, mt = p - ft * nmt;
+    const int k0 = max(a.krange[2 * mt], 0), k1 = min(a.krange[2 * mt + 1], (a.F16 >> 2) - 1);
+    const f32x4 acc = panel_gemm(panel, PP, ft * 16, a.mel_tab, a.M16, mt * 16, k0, k1, col, kq);
+    const int band = mt * 16 + col;
+    float lm[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) lm[i] = __logf(acc[i] + a.eps);
+    if (DCT) {
+      float* lp = lds + (ft * 16 + kq * 4) * LP + band;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) lp[i * LP] = lm[i];
+    } else if (band < a.mel) {
+      mel_store4(a, s, slot, band, (tile0 + ft) * 16 + kq * 4, lm);
+    }
+  }
+  if constexpr (!DCT) return;
+  __syncthreads();
+
+  // ---- phase 3: cepstral coefficients
+  const int nct = a.C16 >> 4;
+  for (int p = wave; p < nct * ntile; p += nw) {
+    const int ft = p / nct, ct = p - ft * nct;
+    const f32x4 acc = panel_gemm(lds, LP, ft * 16, a.dct_tab, a.C16, ct * 16, 0, (a.M16 >> 2) - 1,
+                                 col, kq);
+    const int coef = ct * 16 + col;
+    const float c[4] = {acc[0], acc[1], acc[2], acc[3]};
+    if (coef < a.dct) mel_store4(a, s, slot, coef, (tile0 + ft) * 16 + kq * 4, c);
+  }
+}
+
+template <typename S, bool DCT>
+void launch_nk(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds, hipStream_t st) {
+  const dim3 blk(threads);
+  switch (nk) {
+    case 16: hipLaunchKernelGGL((pool_wave_mel_kernel<S, 16, DCT>), grid, blk, lds, st, a); break;
+    case 32: hipLaunchKernelGGL((pool_wave_mel_kernel<S, 32, DCT>), grid, blk, lds, st, a); break;
+    case 50: hipLaunchKernelGGL((pool_wave_mel_kernel<S, 50, DCT>), grid, blk, lds, st, a); break;
+    case 64: hipLaunchKernelGGL((pool_wave_mel_kernel<S, 64, DCT>), grid, blk, lds, st, a); break;
+    default: hipLaunchKernelGGL((pool_wave_mel_kernel<S, 128, DCT>), grid, blk, lds, st, a);
+  }
+}
+
+}  // namespace
+
+void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st) {
+  const PoolBuildArgs& b = a.b;
+  if (a.mel < 8 || a.mel > 128)
+    throw std::invalid_argument("pool_wave: mel must be 0 or 8..128");
+  if (a.dct < 0 || a.dct > a.mel)
+    throw std::invalid_argument("pool_wave: dct must be 0..mel");
+  if (a.dct && a.fmask_n)
+    throw std::invalid_argument("pool_wave: dct with a frequency mask (bands of cepstral "
+                                "coefficients) is refused");
+  if (a.M16 != ((a.mel + 15) & ~15) || a.C16 != ((a.dct + 15) & ~15))
+    throw std::invalid_argument("pool_wave: M16 and C16 are mel and dct rounded up to 16");
+  if (!a.mel_tab || a.mel_floats != (long long)a.F16 * a.M16)
+    throw std::invalid_argument("pool_wave: the mel table holds F16 rows of M16 floats");
+  if (a.dct && (!a.dct_tab || a.dct_floats != (long long)a.M16 * a.C16))
+    throw std::invalid_argument("pool_wave: the dct table holds M16 rows of C16 floats");
+  const int nmt = a.M16 / 16, ksteps = a.F16 / 4;
+  if (a.krange_n != 2 * nmt)
+    throw std::invalid_argument("pool_wave: krange holds (first, last) per 16-band tile");
+  for (int m = 0; m < nmt; ++m)
+    if (a.krange[2 * m] < 0 || a.krange[2 * m + 1] >= ksteps)
+      throw std::invalid_argument("pool_wave: krange steps must lie in 0..F16/4-1");
+  a.panel_pitch = a.F16 + PANEL_PAD;
+  a.lm_pitch = a.M16 + PANEL_PAD;
+  const int ntiles = (b.W + 15) / 16;
+  auto stretch = [&](int tiles) {
+    const long long lm = a.dct ? (long long)16 * tiles * a.lm_pitch : 0;
+    return std::max(wave_stretch_words(tiles, a.hop, nk), lm);
+  };
+  a.tiles_per_chunk = wave_tiles_per_chunk(a.chunks, b.P, ntiles, [&](int tiles) {
+    return (stretch(tiles) + (long long)16 * tiles * a.panel_pitch) * 4;
+  });
+  const int chunks = (ntiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk;   // (no empty chunk)
+  a.lds_words = (int)wave_stretch_words(a.tiles_per_chunk, a.hop, nk);
+  a.panel_off = (int)stretch(a.tiles_per_chunk);
+  const size_t lds = ((size_t)a.panel_off + (size_t)16 * a.tiles_per_chunk * a.panel_pitch) * 4;
+  const int threads = 64 * std::min(a.F16 / 16, nk > 64 ? 4 : 7);
+  const dim3 grid(b.P, chunks);
+  if (a.f32)
+    a.dct ? launch_nk<float, true>(a, nk, grid, threads, lds, st)
+          : launch_nk<float, false>(a, nk, grid, threads, lds, st);
+  else
+    a.dct ? launch_nk<int16_t, true>(a, nk, grid, threads, lds, st)
+          : launch_nk<int16_t, false>(a, nk, grid, threads, lds, st);
+}

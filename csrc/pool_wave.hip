@@ -47,95 +47,27 @@
 #include "common.h"
 #include "kernels.h"
 #include "pool_geom.h"
+#include "pool_wave_slot.h"
 
 namespace {
-
-constexpr int WAVE_LDS_MAX = 64 * 1024;    // dynamic LDS of one block
-
-MA_DEV float wave_sample(const int16_t* p, int i) { return (float)p[i] * (1.f / 32768.f); }
-MA_DEV float wave_sample(const float* p, int i) { return p[i]; }
 
 template <typename S, int NK>
 __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_kernel(PoolWaveArgs a) {
   extern __shared__ float lds[];
   const PoolBuildArgs& b = a.b;
   const int slot = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
-  const int F = b.H, T = b.W, L = a.L, W = a.n_fft;
+  const int F = b.H, T = b.W;
   if (b.zero && blockIdx.y == 0)
     for (int j = slot * nthr + tid; j < b.nzero; j += gridDim.x * nthr) b.zero[j] = 0.f;
   int64_t gb;
   int t;
   const uint32_t src = pool_src(b, slot, gb, t);
-  int shift = 0, noise_on = 0, clip = 0, off = 0;
-  float gain = 1.f, vol = 0.f;
-  int f0[2] = {0, 0}, fw[2] = {0, 0}, t0[2] = {0, 0}, tw[2] = {0, 0};
-  if (b.augment) {
-    const u32x4 r0 = pool_draw(gb, t, DRAW_WAVE, b.seed);
-    const u32x4 r1 = pool_draw(gb, t, DRAW_WAVE + 1, b.seed);
-    const u32x4 r2 = pool_draw(gb, t, DRAW_WAVE + 2, b.seed);
-    const u32x4 r3 = pool_draw(gb, t, DRAW_WAVE + 3, b.seed);
-    shift = (int)(r0.x % (uint32_t)(2 * a.shift + 1)) - a.shift;
-    gain = fmaf(a.gain_hi - a.gain_lo, u01(r0.y), a.gain_lo);   // (one rounding, by contract)
-    if (a.noise && u01(r0.z) < a.noise_p) {
-      noise_on = 1;
-      clip = (int)(r0.w % (uint32_t)a.Nn);
-      off = (int)(r1.x % (uint32_t)(a.Ln - L + 1));
-      vol = a.vol_max * u01(r1.y);
-    }
-    const uint32_t wr[4] = {r1.z, r2.x, r2.z, r3.x}, sr[4] = {r1.w, r2.y, r2.w, r3.y};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (k < a.fmask_n) {
-        fw[k] = (int)(wr[k] % (uint32_t)(a.fmask_max + 1));
-        f0[k] = (int)(sr[k] % (uint32_t)(F - fw[k] + 1));
-      }
-      if (k < a.tmask_n) {
-        tw[k] = (int)(wr[2 + k] % (uint32_t)(a.tmask_max + 1));
-        t0[k] = (int)(sr[2 + k] % (uint32_t)(T - tw[k] + 1));
-      }
-    }
-  }
-  if (tid == 0 && blockIdx.y == 0) {
-    pool_slot_header(b, slot, src);
-    if (a.params) {
-      float* p = a.params + (size_t)slot * 16;
-      p[0] = (float)shift;
-      p[1] = gain;
-      p[2] = (float)noise_on;
-      p[3] = (float)clip;
-      p[4] = (float)off;
-      p[5] = vol;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        p[6 + 2 * k] = (float)f0[k];
-        p[7 + 2 * k] = (float)fw[k];
-        p[10 + 2 * k] = (float)t0[k];
-        p[11 + 2 * k] = (float)tw[k];
-      }
-      p[14] = p[15] = 0.f;
-    }
-  }
-
-  // ---- stage the chunk's stretch of the padded signal: LDS word i is padded sample q0 + i
+  const WaveSlot s = wave_slot_draws(a, gb, t);
+  if (tid == 0 && blockIdx.y == 0) wave_slot_header(a, slot, src, s);
   const int ntiles = (T + 15) >> 4;
   const int tile0 = blockIdx.y * a.tiles_per_chunk;
   const int ntile = min(a.tiles_per_chunk, ntiles - tile0);
-  const int q0 = tile0 * 16 * a.hop, half = W >> 1;
-  const S* x = (const S*)b.shard + (size_t)src * L;
-  const S* nz = (const S*)a.noise + (size_t)clip * a.Ln + off;
-  for (int i = tid; i < a.lds_words; i += nthr) {
-    const int q = q0 + i;
-    float v = 0.f;
-    if (q < L + W) {
-      int j = q - half;               // reflect: one fold suffices since L > W / 2
-      j = j < 0 ? -j : j;
-      j = j >= L ? 2 * (L - 1) - j : j;
-      const int js = j - shift;
-      v = gain * ((js >= 0 && js < L) ? wave_sample(x, js) : 0.f);
-      if (noise_on) v = fmaf(vol, wave_sample(nz, j), v);
-    }
-    lds[i] = v;
-  }
+  wave_stage<S>(a, s, src, tile0 * 16 * a.hop, lds, tid, nthr);
   __syncthreads();
 
   // ---- table stationary, frames streaming
@@ -152,7 +84,8 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_kernel(PoolWave
       bs[k] = tp[(size_t)(4 * k) * ldt + a.F16];
     }
     const int bin = bt * 16 + col;
-    const bool fmasked = (bin >= f0[0] && bin < f0[0] + fw[0]) || (bin >= f0[1] && bin < f0[1] + fw[1]);
+    const bool fmasked = (bin >= s.f0[0] && bin < s.f0[0] + s.fw[0]) ||
+                         (bin >= s.f0[1] && bin < s.f0[1] + s.fw[1]);
     for (int ft = 0; ft < ntile; ++ft) {
       const float* fp = lds + (ft * 16 + col) * a.hop + kq;
       f32x4 re = {0.f, 0.f, 0.f, 0.f}, im = {0.f, 0.f, 0.f, 0.f};
@@ -170,8 +103,8 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_kernel(PoolWave
         const int tt = tb + i;
         if (tt >= T) break;
         const float pw = re[i] * re[i] + im[i] * im[i] + a.eps;
-        const bool masked = fmasked || (tt >= t0[0] && tt < t0[0] + tw[0]) ||
-                            (tt >= t0[1] && tt < t0[1] + tw[1]);
+        const bool masked = fmasked || (tt >= s.t0[0] && tt < s.t0[0] + s.tw[0]) ||
+                            (tt >= s.t0[1] && tt < s.t0[1] + s.tw[1]);
         bf16x8 px;
         px[0] = masked ? fill : f2bf(a.log_a * __logf(pw) + a.log_b);
 #pragma unroll
@@ -214,41 +147,34 @@ void pool_wave_launch(const PoolWaveArgs& a0, hipStream_t st) {
     throw std::invalid_argument("pool_wave: L must exceed n_fft/2 (reflect padding)");
   if (b.Ns < 1 || b.P < 1 || b.batch < 1)
     throw std::invalid_argument("pool_wave: Ns, P and batch must be positive");
+  if (a.mel < 0 || a.dct < 0 || (a.dct && !a.mel))
+    throw std::invalid_argument("pool_wave: mel and dct are >= 0, dct needs mel");
   const int F = W / 2 + 1, T = 1 + L / a.hop;
-  if (b.H != F || b.W != T || a.F16 != ((F + 15) & ~15))
-    throw std::invalid_argument("pool_wave: the pool is [P][n_fft/2+1][1+L/hop][8]");
+  const int R = a.dct ? a.dct : a.mel ? a.mel : F;      // pool rows
+  if (b.H != R || b.W != T || a.F16 != ((F + 15) & ~15))
+    throw std::invalid_argument("pool_wave: the pool is [P][n_fft/2+1 | mel | dct][1+L/hop][8]");
   if (a.noise && (a.Nn < 1 || a.Ln < L))
     throw std::invalid_argument("pool_wave: the noise bank needs Nn >= 1 clips of Ln >= L samples");
   if (a.noise && (long long)a.Ln - L >= (1 << 24))
     throw std::invalid_argument("pool_wave: Ln - L must stay below 2^24");
   const long long es = a.f32 ? 4 : 2, lim = 1LL << 32;
   if ((long long)b.Ns * L * es >= lim || (a.noise && (long long)a.Nn * a.Ln * es >= lim) ||
-      (long long)b.P * F * T * 16 >= lim)
+      (long long)b.P * R * T * 16 >= lim)
     throw std::invalid_argument("pool_wave: every tensor must stay below 2^32 bytes");
   if (!(a.eps > 0.f))
     throw std::invalid_argument("pool_wave: eps must be positive");
-  if (a.shift < 0 || a.fmask_n < 0 || a.fmask_n > 2 || a.fmask_max < 0 || a.fmask_max > F ||
+  if (a.shift < 0 || a.fmask_n < 0 || a.fmask_n > 2 || a.fmask_max < 0 || a.fmask_max > R ||
       a.tmask_n < 0 || a.tmask_n > 2 || a.tmask_max < 0 || a.tmask_max > T)
     throw std::invalid_argument("pool_wave: shift >= 0, masks are (n <= 2, max <= size)");
   const int nk = pool_wave_ksteps(W);
   if (a.tab_floats != (long long)4 * nk * 2 * a.F16)
     throw std::invalid_argument("pool_wave: the table holds 4*ksteps rows of 2*F16 floats");
-  // Frame chunks per slot, by measurement (README, "Waveform front end": 4 of 2..11 win at P = 320
-  // with 11 tiles, 6 at P = 32): about 1024 blocks in all, never fewer than two 16-frame tiles per
-  // block, and then as many more as the LDS stretch [0, (16 tiles - 1) * hop + 4 nk) words needs.
+  if (a.mel) return pool_mel_launch(a, nk, st);
   const int ntiles = (T + 15) / 16;
-  auto words = [&](int tiles) { return (long long)(16 * tiles - 1) * a.hop + 4 * nk; };
-  int chunks = a.chunks;
-  if (chunks < 0 || chunks > ntiles)
-    throw std::invalid_argument("pool_wave: chunks must be 0..number of 16-frame tiles");
-  if (!chunks)
-    for (chunks = std::max(1, std::min((1024 + b.P - 1) / b.P, (ntiles + 1) / 2));
-         chunks < ntiles && words((ntiles + chunks - 1) / chunks) * 4 > WAVE_LDS_MAX;)
-      ++chunks;
-  a.tiles_per_chunk = (ntiles + chunks - 1) / chunks;
-  chunks = (ntiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk;   // (no empty chunk)
-  if (words(a.tiles_per_chunk) * 4 > WAVE_LDS_MAX)
-    throw std::invalid_argument("pool_wave: the chunk's waveform stretch exceeds the LDS limit");
+  auto words = [&](int tiles) { return wave_stretch_words(tiles, a.hop, nk); };
+  a.tiles_per_chunk = wave_tiles_per_chunk(a.chunks, b.P, ntiles,
+                                           [&](int tiles) { return words(tiles) * 4; });
+  const int chunks = (ntiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk;   // (no empty chunk)
   a.lds_words = (int)words(a.tiles_per_chunk);
   const int waves = std::min(a.F16 / 16, nk > 64 ? 4 : 7);
   const dim3 grid(b.P, chunks);

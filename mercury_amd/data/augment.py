@@ -693,6 +693,17 @@ class WaveRecipe:
        ``SpecRecipe``'s width and start formulas on (F, T);
     6. one rounding to bf16, channel 0 of the NHWC8 pixel (row k, column t); channels 1..7 +0.
 
+    With ``mel = M > 0`` (``pool_wave_mel_kernel``, ``csrc/pool_mel.hip``) step 4 becomes
+    ``mel[t][m] = sum_k (re^2 + im^2)[t][k] fb[k][m]``, ``lm = ln(mel + eps)``, ``y[m][t] = a lm +
+    b``; ``fb`` is torchaudio's default bank (HTK scale ``mel(f) = 2595 log10(1 + f/700)``, no
+    area normalisation): M + 2 points equally spaced in mel from ``mel(fmin)`` to ``mel(fmax)``
+    map back to ``f_0..f_{M+1}`` Hz, the bins lie at ``g_k = k (sr/2) / (F-1)``, and ``fb[k][m] =
+    max(0, min((g_k - f_m)/(f_{m+1} - f_m), (f_{m+2} - g_k)/(f_{m+2} - f_{m+1})))``.  A filter
+    with no bin under it gives ``a ln(eps) + b``.  With ``dct = C > 0`` as well, ``c[t][j] = sum_m
+    lm[t][m] D[m][j]``, ``D[m][j] = sqrt(2/M) cos(pi (m + 0.5) j / M)`` with column 0 scaled by
+    ``sqrt(1/2)`` (orthonormal DCT-II), and ``y[j][t] = a c + b``.  The output has R = C, else
+    M, else F rows; masks are drawn on (R, T), and a frequency mask with ``dct`` is refused.
+
     Draws, per pool slot (Philox on the image kernels' counter ``(gb, t)``, stream words
     0x5bec8..0x5becb of its own): ``s = r % (2*shift + 1) - shift``; ``gain = fma(hi - lo,
     u01(r), lo)``, one rounding; noise on iff ``u01(r) < p``, then ``clip = r % Nn``, ``off = r % (Ln - L + 1)``,
@@ -708,11 +719,18 @@ class WaveRecipe:
     fmask: Tuple[int, int] = (0, 0)
     tmask: Tuple[int, int] = (0, 0)
     fill: float = 0.0
+    mel: int = 0                                    # mel bands (0: the linear bins)
+    sr: int = 16000                                 # sample rate, Hz (mel only)
+    fmin: float = 0.0
+    fmax: Optional[float] = None                    # None: sr / 2
+    dct: int = 0                                    # cepstral coefficients kept (0: log-mel)
 
     def __post_init__(self):
         s = object.__setattr__
-        for k in ('n_fft', 'hop', 'shift'):
+        for k in ('n_fft', 'hop', 'shift', 'mel', 'sr', 'dct'):
             s(self, k, int(getattr(self, k)))
+        s(self, 'fmin', float(self.fmin))
+        s(self, 'fmax', None if self.fmax is None else float(self.fmax))
         s(self, 'fmask', _mask(self.fmask, 'fmask'))
         s(self, 'tmask', _mask(self.tmask, 'tmask'))
         s(self, 'fill', float(self.fill))
@@ -737,11 +755,28 @@ class WaveRecipe:
             raise ValueError('WaveRecipe: norm is (mean, std), std > 0, got %r' % (self.norm,))
         if not math.isfinite(self.fill):
             raise ValueError('WaveRecipe: fill is finite, got %r' % self.fill)
+        if self.mel and not 8 <= self.mel <= 128:
+            raise ValueError('WaveRecipe: mel is 0 or 8..128, got %d' % self.mel)
+        if self.sr < 1:
+            raise ValueError('WaveRecipe: sr is positive, got %d' % self.sr)
+        top = self.sr / 2 if self.fmax is None else self.fmax
+        if not 0 <= self.fmin < top:
+            raise ValueError('WaveRecipe: fmin is 0 <= fmin < fmax, got %r (fmax %r)'
+                             % (self.fmin, top))
+        if not top <= self.sr / 2:
+            raise ValueError('WaveRecipe: fmax is at most sr/2 = %r, got %r' % (self.sr / 2, top))
+        if not 0 <= self.dct <= self.mel:
+            raise ValueError('WaveRecipe: dct is 0..mel (and needs mel > 0), got dct = %d, '
+                             'mel = %d' % (self.dct, self.mel))
+        if self.dct and self.fmask[0] > 0:
+            raise ValueError('WaveRecipe: fmask with dct (bands of cepstral coefficients) is '
+                             'refused, got fmask = %r' % (self.fmask,))
 
     @classmethod
     def parse(cls, spec):
         """``wave:nfft=200,hop=100,shift=1600,gain=0.8:1.2,noise=0.8x0.1,eps=1e-6,norm=-5:4,
-        fmask=2x10,tmask=2x20,fill=0`` (the ``wave:`` prefix is optional here)."""
+        fmask=2x10,tmask=2x20,fill=0,mel=80,sr=16000,fmin=0,fmax=8000,dct=13`` (the ``wave:``
+        prefix is optional here)."""
         spec = spec.strip()
         if spec.startswith('wave:'):
             spec = spec[5:]
@@ -750,7 +785,7 @@ class WaveRecipe:
             if '=' not in item:
                 raise ValueError('WaveRecipe.parse: %r is not name=value' % item)
             k, v = (s.strip() for s in item.split('=', 1))
-            if k in ('nfft', 'hop', 'shift'):
+            if k in ('nfft', 'hop', 'shift', 'mel', 'sr', 'dct'):
                 kw['n_fft' if k == 'nfft' else k] = int(v)
             elif k in ('fmask', 'tmask', 'noise'):
                 nm = v.split('x')
@@ -769,8 +804,10 @@ class WaveRecipe:
                     raise ValueError('WaveRecipe.parse: %s is A:B, got %r' % (k, v))
                 else:
                     kw[k] = (float(g[0]), float(g[1]))
-            elif k in ('fill', 'eps'):
+            elif k in ('fill', 'eps', 'fmin'):
                 kw[k] = float(v)
+            elif k == 'fmax':
+                kw[k] = None if v in ('', 'none') else float(v)
             else:
                 raise ValueError('WaveRecipe.parse: unknown key %r' % k)
         return cls(**kw)
@@ -786,6 +823,11 @@ class WaveRecipe:
         if self.norm is not None:
             out.append('norm=%r:%r' % self.norm)
         out += ['fmask=%dx%d' % self.fmask, 'tmask=%dx%d' % self.tmask, 'fill=%r' % self.fill]
+        if self.mel:
+            out += ['mel=%d' % self.mel, 'sr=%d' % self.sr, 'fmin=%r' % self.fmin]
+            if self.fmax is not None:
+                out.append('fmax=%r' % self.fmax)
+            out.append('dct=%d' % self.dct)
         return 'wave:' + ','.join(out)
 
     @property
@@ -795,8 +837,9 @@ class WaveRecipe:
                 and 0 in self.fmask and 0 in self.tmask)
 
     def out_hw(self, L):
-        """(F, T): bins and frames of an L-sample clip, the network's input size."""
-        return self.n_fft // 2 + 1, 1 + L // self.hop
+        """(R, T): rows and frames of an L-sample clip, the network's input size.  R is ``dct``
+        if set, else ``mel`` if set, else the F = n_fft/2 + 1 bins."""
+        return self.dct or self.mel or self.n_fft // 2 + 1, 1 + L // self.hop
 
     def affine(self):
         """(a, b) of ``y = a ln(power + eps) + b``."""
@@ -811,7 +854,8 @@ class WaveRecipe:
                              % (self.n_fft, L))
         F, T = self.out_hw(L)
         if self.fmask[1] > F:
-            raise ValueError('WaveRecipe: fmask width %d exceeds F = %d' % (self.fmask[1], F))
+            raise ValueError('WaveRecipe: fmask width %d exceeds the %d rows'
+                             % (self.fmask[1], F))
         if self.tmask[1] > T:
             raise ValueError('WaveRecipe: tmask width %d exceeds T = %d' % (self.tmask[1], T))
         if self.noise is not None and noise_shape is None:
@@ -866,12 +910,65 @@ class WaveRecipe:
         tab[:W, F16:F16 + F] = -w * torch.sin(ang)
         return tab.to(torch.float32)
 
+    def _mel_fb(self):
+        """fp64 [F][M]: the triangular HTK filter bank of the class docstring."""
+        F, M = self.n_fft // 2 + 1, self.mel
+
+        def to_mel(f):
+            return 2595.0 * math.log10(1.0 + f / 700.0)
+        top = self.sr / 2 if self.fmax is None else self.fmax
+        pts = torch.linspace(to_mel(self.fmin), to_mel(top), M + 2, dtype=torch.float64)
+        f = 700.0 * (10.0 ** (pts / 2595.0) - 1.0)                       # [M + 2] Hz
+        g = torch.arange(F, dtype=torch.float64).view(F, 1) * (self.sr / 2) / (F - 1)
+        up = (g - f[:M]) / (f[1:M + 1] - f[:M])
+        down = (f[2:] - g) / (f[2:] - f[1:M + 1])
+        return torch.minimum(up, down).clamp_(min=0.0)
+
+    def _dct_mat(self):
+        """fp64 [M][dct]: the first ``dct`` columns of the orthonormal DCT-II."""
+        M = self.mel
+        m = torch.arange(M, dtype=torch.float64).view(M, 1)
+        j = torch.arange(self.dct, dtype=torch.float64).view(1, self.dct)
+        D = math.sqrt(2.0 / M) * torch.cos(math.pi * (m + 0.5) * j / M)
+        D[:, 0] *= math.sqrt(0.5)
+        return D
+
+    def mel_table(self):
+        """The kernel's filter bank, fp64 -> fp32 [F16][M16], zero padding rows and columns."""
+        if not self.mel:
+            raise ValueError('mel_table: the recipe has mel = 0')
+        F = self.n_fft // 2 + 1
+        tab = torch.zeros((F + 15) // 16 * 16, (self.mel + 15) // 16 * 16, dtype=torch.float64)
+        tab[:F, :self.mel] = self._mel_fb()
+        return tab.to(torch.float32)
+
+    def dct_table(self):
+        """The kernel's DCT, fp64 -> fp32 [M16][C16]; rows ``>= mel`` are zero (the padded mel
+        columns hold ``ln(eps)``, not 0) and so are the padding columns."""
+        if not self.dct:
+            raise ValueError('dct_table: the recipe has dct = 0')
+        tab = torch.zeros((self.mel + 15) // 16 * 16, (self.dct + 15) // 16 * 16,
+                          dtype=torch.float64)
+        tab[:self.mel, :self.dct] = self._dct_mat()
+        return tab.to(torch.float32)
+
+    def mel_ksteps(self):
+        """Per tile of 16 mel bands, the first and last step of 4 bins in which ``mel_table``
+        holds a nonzero: a flat list (first, last, first, last, ...), the kernel's K ranges.  A
+        tile of empty filters gets (0, -1)."""
+        tab = self.mel_table()
+        out = []
+        for m0 in range(0, tab.shape[1], 16):
+            rows = torch.nonzero(tab[:, m0:m0 + 16].abs().sum(1))
+            out += [int(rows.min()) // 4, int(rows.max()) // 4] if len(rows) else [0, -1]
+        return out
+
     # ---------------------------------------------------------------- CPU reference
     def reference(self, x, noise, params, dtype=torch.bfloat16):
         """The recipe on one clip ``x[L]`` (int16 or float) with explicit draws ``params``
         (``WAVE_PARAMS`` values, the kernel's layout) and the noise bank ``noise`` ([Nn][Ln] or
-        None) -> [F][T][8] ``dtype``, the pool's layout.  fp64 from step 1 on, then one rounding
-        to ``dtype``."""
+        None) -> [R][T][8] ``dtype``, the pool's layout (``out_hw``).  fp64 from step 1 on, then one
+        rounding to ``dtype``."""
         def f64(t):
             t = torch.as_tensor(t)
             return t.double() / 32768 if t.dtype == torch.int16 else t.double()
@@ -895,15 +992,21 @@ class WaveRecipe:
             xa = xa + p[5] * f64(noise[clip, off:off + L])
         h = W // 2
         xp = torch.cat([xa[1:h + 1].flip(0), xa, xa[L - h - 1:L - 1].flip(0)])
-        F, T = self.out_hw(L)
+        F, T = self.out_hw(L)                      # (rows of the output)
         n = torch.arange(W, dtype=torch.float64).view(W, 1)
-        k = torch.arange(F, dtype=torch.float64).view(1, F)
+        k = torch.arange(W // 2 + 1, dtype=torch.float64).view(1, W // 2 + 1)
         w = 0.5 - 0.5 * torch.cos(2 * math.pi * n / W)
         ang = 2 * math.pi * ((n * k) % W) / W
         frames = xp.unfold(0, W, hop)[:T]                               # [T][W]
         re, im = frames @ (w * torch.cos(ang)), frames @ (-w * torch.sin(ang))
         a, b = self.affine()
-        y = (a * torch.log(re * re + im * im + self.eps) + b).t()       # [F][T]
+        if self.mel:
+            y = torch.log((re * re + im * im) @ self._mel_fb() + self.eps)     # [T][M]
+            if self.dct:
+                y = y @ self._dct_mat()
+            y = (a * y + b).t()                                         # [R][T]
+        else:
+            y = (a * torch.log(re * re + im * im + self.eps) + b).t()   # [F][T]
         f = torch.arange(F).view(F, 1)
         t = torch.arange(T).view(1, T)
         masked = torch.zeros(F, T, dtype=torch.bool)

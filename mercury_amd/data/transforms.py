@@ -295,7 +295,9 @@ class SpecAugment(object):
 
 class WaveSpectrogram(object):
     """A ``WaveRecipe`` (``data/augment.py``: shift, gain and background noise on the raw clip,
-    then the log-spectrogram) on one waveform [L] (int16 PCM or float) -> float32 [1][F][T].
+    then the log-spectrogram, or with ``mel`` / ``dct`` set the log-mel bands or cepstral
+    coefficients) on one waveform [L] (int16 PCM or float) -> float32 [1][R][T], (R, T) =
+    ``recipe.out_hw(L)``.
     The draws come from torch's RNG (``generator``) through ``WaveRecipe.draw``, the arithmetic
     is ``WaveRecipe.reference``; ``noise`` is the bank [Nn][Ln] a ``noise=`` recipe mixes from,
     ``augment=False`` the evaluation transform (identity draws).  The eager ``Trainer`` runs it

@@ -902,8 +902,10 @@ class NativeEngine(object):
             raise ValueError('empty shard')
         if self.noise is not None and self.noise.dtype != x.dtype:
             raise ValueError('noise bank is %s but the shard is %s' % (self.noise.dtype, x.dtype))
-        if isinstance(self.augment, WaveRecipe):     # the DFT table, before any graph capture
+        if isinstance(self.augment, WaveRecipe):     # the tables, before any graph capture
             ops.importance.pool_wave_table(self.augment, self.device)
+            if self.augment.mel:
+                ops.importance.pool_mel_tables(self.augment, self.device)
         if self.augment is not None and self.aug_params is None:
             n = SPEC_PARAMS if isinstance(self.augment, SpecRecipe) else \
                 WAVE_PARAMS if isinstance(self.augment, WaveRecipe) else \

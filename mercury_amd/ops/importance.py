@@ -35,9 +35,12 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
     log-spectrogram) takes an int16 or float32 shard of raw clips [Ns][L], an optional ``noise``
     bank [Nn][Ln] of the same dtype and a pool [P][n_fft/2+1][1+L//hop][8]
     (``pool_wave_kernel``); ``params`` is then fp32 [P][16] (``data.augment.WAVE_PARAMS``).
+    With ``mel`` (and ``dct``) set the pool is [P][R][1+L//hop][8], R = ``recipe.out_hw(L)[0]``
+    log-mel bands or cepstral coefficients (``pool_wave_mel_kernel``, ``csrc/pool_mel.hip``).
     ``augment=False`` draws the identity and still transforms.  The first build for an
-    ``(n_fft, device)`` makes the DFT table (an allocation and a copy): inside a graph capture
-    only after such a call or ``pool_wave_table`` (``NativeEngine.set_shard`` makes it)."""
+    ``(n_fft, device)`` makes the DFT table (an allocation and a copy), the first for a mel
+    recipe its filter-bank and DCT tables: inside a graph capture only after such a call or
+    ``pool_wave_table`` / ``pool_mel_tables`` (``NativeEngine.set_shard`` makes them)."""
     _chk(labels, torch.int64, 'labels')
     if isinstance(recipe, WaveRecipe):
         if force_augment_kernel:
@@ -152,6 +155,21 @@ def pool_wave_table(recipe, device):
     return _WAVE_TABLES[key]
 
 
+_MEL_TABLES = {}     # (n_fft, mel, sr, fmin, fmax, dct, device) -> (mel table, dct table | None,
+#                      K ranges), built once (never inside a capture)
+
+
+def pool_mel_tables(recipe, device):
+    """``(mel_table, dct_table or None, mel_ksteps)`` of a mel recipe, the tables resident on
+    ``device``."""
+    key = (recipe.n_fft, recipe.mel, recipe.sr, recipe.fmin, recipe.fmax, recipe.dct, str(device))
+    if key not in _MEL_TABLES:
+        _MEL_TABLES[key] = (recipe.mel_table().to(device),
+                            recipe.dct_table().to(device) if recipe.dct else None,
+                            recipe.mel_ksteps())
+    return _MEL_TABLES[key]
+
+
 def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, augment,
                shuffle, zero, recipe, params, chunks=0):
     if shard.dtype not in (torch.int16, torch.float32) or shard.dim() != 2:
@@ -172,6 +190,12 @@ def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batc
     if params is not None:
         _chk(params, torch.float32, 'params', P * WAVE_PARAMS)
     tab = pool_wave_table(recipe, shard.device)
+    mel = {}
+    if recipe.mel:
+        mtab, dtab, krange = pool_mel_tables(recipe, shard.device)
+        mel = dict(mel=recipe.mel, dct=recipe.dct, mel_tab=ptr(mtab), mel_floats=mtab.numel(),
+                   dct_tab=ptr(dtab), dct_floats=dtab.numel() if dtab is not None else 0,
+                   krange=krange)
     glo, ghi = recipe.gain or (1.0, 1.0)
     p, vol = recipe.noise or (0.0, 0.0)
     a, b = recipe.affine()
@@ -186,7 +210,8 @@ def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batc
                     seed=int(seed) & 0xffffffff, shift=recipe.shift, gain_lo=glo, gain_hi=ghi,
                     noise_p=p, vol_max=vol, eps=recipe.eps, log_a=a, log_b=b,
                     fmask_n=recipe.fmask[0], fmask_max=recipe.fmask[1], tmask_n=recipe.tmask[0],
-                    tmask_max=recipe.tmask[1], fill=recipe.fill, chunks=chunks)
+                    tmask_max=recipe.tmask[1], fill=recipe.fill, chunks=chunks,
+                    **mel)
 
 
 def is_sample(losses, ema, ctrl, idx, w, P, B, group, alpha=0.5, ema_alpha=0.9, seed=0,
