@@ -656,6 +656,38 @@ PYBIND11_MODULE(_C, m) {
     check_launch("attn_pool_bwd");
   });
 
+  // the speech LSTM's classifier head (fc_head.hip)
+  m.def("fc_head_fwd", [](uintptr_t z, uintptr_t m0, uintptr_t m1, uintptr_t w1, uintptr_t b1,
+                          uintptr_t gamma, uintptr_t beta, uintptr_t run_mean, uintptr_t run_var,
+                          uintptr_t batches, uintptr_t w2, uintptr_t b2, uintptr_t y,
+                          uintptr_t mean, uintptr_t rstd, uintptr_t a2, uintptr_t logits, int B,
+                          int K, int N, int C, float scale, float eps, float momentum, int train,
+                          uintptr_t st) {
+    fc_head_fwd_launch(FcHeadFwdArgs{P<const float>(z), P<const uint8_t>(m0), P<const uint8_t>(m1),
+                                     P<const float>(w1), P<const float>(b1), P<const float>(gamma),
+                                     P<const float>(beta), P<float>(run_mean), P<float>(run_var),
+                                     P<long long>(batches), P<const float>(w2), P<const float>(b2),
+                                     P<float>(y), P<float>(mean), P<float>(rstd), P<bf16>(a2),
+                                     P<float>(logits), B, K, N, C, scale, eps, momentum, train},
+                       S(st));
+    check_launch("fc_head_fwd");
+  });
+  m.def("fc_head_bwd", [](uintptr_t dlogits, uintptr_t z, uintptr_t m0, uintptr_t m1, uintptr_t w1,
+                          uintptr_t w2, uintptr_t gamma, uintptr_t y, uintptr_t mean,
+                          uintptr_t rstd, uintptr_t a2, uintptr_t dy, uintptr_t dz, uintptr_t dw1,
+                          uintptr_t db1, uintptr_t dgamma, uintptr_t dbeta, uintptr_t dw2,
+                          uintptr_t db2, int B, int K, int N, int C, float scale, int train,
+                          uintptr_t st) {
+    fc_head_bwd_launch(FcHeadBwdArgs{P<const float>(dlogits), P<const float>(z),
+                                     P<const uint8_t>(m0), P<const uint8_t>(m1), P<const float>(w1),
+                                     P<const float>(w2), P<const float>(gamma), P<const float>(y),
+                                     P<const float>(mean), P<const float>(rstd), P<const bf16>(a2),
+                                     P<bf16>(dy), P<float>(dz), P<float>(dw1), P<float>(db1),
+                                     P<float>(dgamma), P<float>(dbeta), P<float>(dw2), P<float>(db2),
+                                     B, K, N, C, scale, train}, S(st));
+    check_launch("fc_head_bwd");
+  });
+
   m.def("pool_build", [](uintptr_t shard, uintptr_t labels, uintptr_t ctrl, uintptr_t pool,
                          uintptr_t pool_label, uintptr_t pool_index, int Ns, int H, int W, int Pn,
                          int batch, int pad, int flip, int augment, int shuffle, uint32_t seed,

@@ -523,3 +523,57 @@ struct AttnBwdArgs {
   int T, B, D, bf16_x;
 };
 void attn_pool_bwd_launch(const AttnBwdArgs& a, hipStream_t st);
+// the speech LSTM's classifier head (fc_head.hip): Linear(K, N) + BatchNorm1d(N) + ReLU +
+// Linear(N, C) around two dropouts.  Masks are uint8 keep-masks (null = keep all) and ``scale``
+// the value of a kept element; N % 16 == 0, K % 32 == 0.  One block owns 16 columns of N for all
+// B rows, so the batch statistics need no second launch.
+constexpr int FC_HEAD_MAX_B = 320;      // 20 row tiles of 16: the largest instantiation
+constexpr int FC_HEAD_MAX_C = 1024;
+struct FcHeadFwdArgs {
+  const float* z;                 // [B][K]
+  const uint8_t* m0;              // [B][K] keep-mask of z, or null
+  const uint8_t* m1;              // [B][N] keep-mask of the ReLU output, or null
+  const float* w1;                // [N][K]
+  const float* b1;                // [N]
+  const float* gamma;             // [N]
+  const float* beta;              // [N]
+  float* run_mean;                // [N]: read (eval) or updated (train); null in train = no update
+  float* run_var;                 // [N]
+  long long* batches;             // num_batches_tracked, incremented in train; or null
+  const float* w2;                // [C][N]
+  const float* b2;                // [C]
+  float* y;                       // [B][N] the Linear's output, kept for the backward; or null
+  float* mean;                    // [N] the statistics the BN used
+  float* rstd;                    // [N]
+  bf16* a2;                       // [B][N]
+  float* logits;                  // [B][C]
+  int B, K, N, C;
+  float scale, eps, momentum;
+  int train;                      // 1: batch statistics (B >= 2), 0: the running pair
+};
+void fc_head_fwd_launch(const FcHeadFwdArgs& a, hipStream_t st);   // fc_bn_fwd + fc_out
+struct FcHeadBwdArgs {
+  const float* dlogits;           // [B][C]
+  const float* z;                 // as the forward read it
+  const uint8_t* m0;
+  const uint8_t* m1;
+  const float* w1;
+  const float* w2;
+  const float* gamma;
+  const float* y;                 // saved by the forward
+  const float* mean;
+  const float* rstd;
+  const bf16* a2;
+  bf16* dy;                       // [B][N] workspace: fc_bn_bwd writes it, fc_dz reads it
+  float* dz;                      // [B][K]
+  float* dw1;                     // [N][K]
+  float* db1;                     // [N]
+  float* dgamma;                  // [N]
+  float* dbeta;                   // [N]
+  float* dw2;                     // [C][N]
+  float* db2;                     // [C]
+  int B, K, N, C;
+  float scale;
+  int train;                      // as the forward's
+};
+void fc_head_bwd_launch(const FcHeadBwdArgs& a, hipStream_t st);   // fc_bn_bwd + fc_dz

@@ -24,6 +24,13 @@ It reaches only layers that take the native cell; ``cell='torch'`` with ``proj='
 ``impl``): the eager torch chain (default), the HIP kernels of ``csrc/attn.hip``, or those only at
 the shapes where they were measured not slower (``ops.attention.MEASURED_NATIVE``).
 
+``head`` picks how the classifier tail (dropout, ``fc1``, dropout, ``fc2``) runs, in the same
+three values: the torch modules (default), the HIP kernels of ``csrc/fc_head.hip``
+(``ops.fc_head.fc_head``: bf16 operands, fp32 sums and BatchNorm arithmetic, the modules' own
+parameters and buffers; dropout masks drawn with torch, though not the draws ``nn.Dropout`` would
+make; a CPU input is a ``ValueError``), or those only on the GPU at the (batch, width, classes)
+sizes in ``ops.fc_head.MEASURED_NATIVE``.
+
 ``packed`` decides whether the two recurrent layers honour ``lengths``.  ``packed=True`` is the
 reference's intended model, a packed-sequence model: each layer computes what
 ``pad_packed_sequence(lstm(pack_padded_sequence(x, lengths, enforce_sorted=False)),
@@ -104,7 +111,7 @@ class Attention(nn.Module):
 
 class MyLSTM(nn.Module):
     def __init__(self, feature_dim, num_classes, hidden_dim=512, lstm_layer=2, dropout=0.2,
-                 cell='torch', attn='torch', packed=False, proj='torch'):
+                 cell='torch', attn='torch', packed=False, proj='torch', head='torch'):
         super().__init__()
         if cell not in ('torch', 'native', 'auto'):
             raise ValueError("cell must be 'torch', 'native' or 'auto', got %r" % (cell,))
@@ -112,6 +119,8 @@ class MyLSTM(nn.Module):
             raise ValueError("attn must be 'torch', 'native' or 'auto', got %r" % (attn,))
         if proj not in _IMPLS:
             raise ValueError("proj must be 'torch', 'native' or 'auto', got %r" % (proj,))
+        if head not in _IMPLS:
+            raise ValueError("head must be 'torch', 'native' or 'auto', got %r" % (head,))
         if proj == 'native' and cell == 'torch':
             raise ValueError("proj='native' needs the native cell: cell='native' or 'auto'")
         if not isinstance(packed, bool):
@@ -120,6 +129,7 @@ class MyLSTM(nn.Module):
         self.attn = attn
         self.packed = packed
         self.proj = proj
+        self.head = head
         self.dropout = nn.Dropout(p=dropout)
         self.lstm1 = nn.LSTM(feature_dim, hidden_dim, num_layers=1, bidirectional=True)
         self.atten1 = Attention(hidden_dim * 2, batch_first=True, impl=attn)
@@ -170,5 +180,10 @@ class MyLSTM(nn.Module):
         out2 = self._layer(self.lstm2, out1, lengths)
         b, _ = self.atten2(out2.transpose(0, 1), lengths)
         z = torch.cat([a, b], dim=1)
+        if self.head != 'torch':
+            from ..ops import fc_head as native
+            if self.head == 'native' or (z.is_cuda and (
+                    z.shape[0], z.shape[1], self.fc2.out_features) in native.MEASURED_NATIVE):
+                return native.fc_head(z, self.fc1, self.fc2, self.dropout.p, self.training)
         z = self.fc1(self.dropout(z))
         return self.fc2(self.dropout(z))

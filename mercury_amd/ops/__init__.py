@@ -120,6 +120,8 @@ from .lstm import (lstm_step_fwd, lstm_step_bwd, pack_lstm, BiLSTMFunction, bils
                    MEASURED_NATIVE, MEASURED_NATIVE_PACKED, MEASURED_NATIVE_PROJ,
                    lstm_proj_fwd, lstm_proj_dx, lstm_proj_wgrad)
 from .attention import attn_pool_fwd, attn_pool_bwd, AttnPoolFunction, attn_pool  # noqa: E402
+# (the front-end function fc_head.fc_head is not re-exported: the name is the submodule's)
+from .fc_head import fc_head_fwd, fc_head_bwd, FcHeadFunction  # noqa: E402
 
 __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_fwd', 'pwconv_fwd', 'stem_fwd', 'conv_dgrad', 'conv_wgrad', 'conv_bwd', 'pick_tiles',
            'pack_conv_weight', 'to_nhwc', 'from_nhwc', 'bn_apply', 'bn_bwd', 'BnRunTable', 'sums_numel', 'sums_total', 'streaming_stores',
@@ -130,4 +132,4 @@ __all__ = ['lib', 'available', 'ConvSpec', 'conv_fwd', 'conv_fwd_dual', 'pgemm_f
            'nchw_to_nhwc8', 'lstm_step_fwd', 'lstm_step_bwd', 'lstm_proj_fwd', 'lstm_proj_dx',
            'lstm_proj_wgrad', 'pack_lstm', 'BiLSTMFunction', 'bilstm',
            'emulate', 'MEASURED_NATIVE', 'attn_pool_fwd', 'attn_pool_bwd', 'AttnPoolFunction',
-           'attn_pool']
+           'attn_pool', 'fc_head_fwd', 'fc_head_bwd', 'FcHeadFunction']
