@@ -25,6 +25,12 @@ its ``torch_*`` fields proj='torch' (``torch_proj_us`` instead of ``torch_bf16_u
 ``torch_min_us`` is the fastest proj='torch' run: ops.lstm.MEASURED_NATIVE_PROJ lists the
 (B, F, H) at which ``native_us <= torch_min_us`` in both modes.
 
+``--recur persistent`` does the same for the recurrence: ``bilstm(recur='persistent')`` (one
+launch per layer pass, csrc/lstm_persist.hip) against ``bilstm(recur='step')``; the record's
+``native_*`` fields are the persistent route, ``torch_*`` the step kernels (``step_us``), and
+ops.lstm.MEASURED_PERSISTENT lists the (B, H) at which ``native_us < torch_min_us`` in both modes
+on both layers.
+
     python bench/lstm_bench.py [--out profiles/r8/lstm/lstm_bench.jsonl] [--quick]
     python bench/lstm_bench.py --proj native --out profiles/r20/lstm_proj/lstm_bench.jsonl
 """
@@ -55,7 +61,7 @@ def _lens(kind, T, B, seed):
     return [int(v) for v in torch.randint(T // 2, T + 1, (B,), generator=g)]
 
 
-def _runners(T, B, F, H, train, lens=None, proj='torch'):
+def _runners(T, B, F, H, train, lens=None, proj='torch', recur='step'):
     import torch
     from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
     from mercury_amd.ops import lstm as L
@@ -76,6 +82,9 @@ def _runners(T, B, F, H, train, lens=None, proj='torch'):
         xin = xin.detach().requires_grad_()
         f(xin, m).backward(g)
 
+    if recur == 'persistent':
+        return ((lambda: run(lambda a, m: L.bilstm(a, m, recur='persistent'), lstm, x, gout)),
+                (lambda: run(L.bilstm, lstm, x, gout)), None)
     if proj == 'native':
         return ((lambda: run(lambda a, m: L.bilstm(a, m, proj='native'), lstm, x, gout)),
                 (lambda: run(L.bilstm, lstm, x, gout)), None)
@@ -137,9 +146,13 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--proj', choices=('torch', 'native'), default='torch',
                     help="native: bilstm(proj='native') against bilstm(proj='torch')")
+    ap.add_argument('--recur', choices=('step', 'persistent'), default='step',
+                    help="persistent: bilstm(recur='persistent') against bilstm(recur='step')")
     args = ap.parse_args()
     if args.proj == 'native' and args.lengths != 'none':
         ap.error('--proj native is measured without lengths')
+    if args.recur == 'persistent' and (args.lengths != 'none' or args.proj != 'torch'):
+        ap.error('--recur persistent is measured without lengths, with proj=torch')
     import torch
     shapes = SHAPES[:1] if args.quick else SHAPES
     if args.only:
@@ -150,7 +163,8 @@ def main():
         for name, T, B, F, H in shapes:
             for train in (False, True):
                 lens = _lens(args.lengths, T, B, args.seed)
-                native, torch_ref, native_dev = _runners(T, B, F, H, train, lens, args.proj)
+                native, torch_ref, native_dev = _runners(T, B, F, H, train, lens, args.proj,
+                                                         args.recur)
                 tn, tt, td, en, et = [], [], [], [], []
                 hn, ht, hd = ['graph'], ['graph'], ['graph']
                 for _ in range(rounds):
@@ -174,6 +188,13 @@ def main():
                     rec['torch_proj_us'] = rec.pop('torch_bf16_us')
                     rec['torch_min_us'] = round(min(tt), 1)
                     rec['not_slower'] = rec['native_us'] <= rec['torch_min_us']
+                if args.recur == 'persistent':
+                    rec['recur'] = 'persistent'
+                    rec['step_us'] = rec.pop('torch_bf16_us')
+                    rec['torch_min_us'] = round(min(tt), 1)
+                    rec['faster'] = rec['native_us'] < rec['torch_min_us']
+                    from mercury_amd.ops import lstm as L
+                    L.persist_check(L.persist_workspace('cuda'))
                 if lens is not None:
                     rec.update({'lengths': args.lengths, 'seed': args.seed, 'max_len': max(lens),
                                 'mean_len': round(sum(lens) / len(lens), 1),

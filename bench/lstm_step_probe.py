@@ -15,6 +15,8 @@ fp32 result, fp32 operands, bf16 result) and the [T][B][2][4H] -> [T][2][B][4H] 
 length T, or lengths uniform in [T/2, T] (``--seed``); ``uniform`` also times the launches cut
 to max(len_b) steps, as host-side lengths run them (still divided by T).  A build with
 ``-DLSTM_NO_WAVE_SKIP`` keeps all-padded waves in the K loop, for what the skip buys.
+``--recur persistent`` times the one-launch kernels of csrc/lstm_persist.hip instead (the
+sequence time over T, the same columns, with and without ``--lengths``).
 One JSON line per run, appended to ``--out``.
 """
 from __future__ import annotations
@@ -36,14 +38,16 @@ def main():
     ap.add_argument('--gemm', action='store_true')
     ap.add_argument('--lengths', choices=('none', 'full', 'uniform'), default='none')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--recur', choices=('step', 'persistent'), default='step')
     args = ap.parse_args()
     import torch
     from gtime import gtime
     from mercury_amd.ops import lstm as L
+    persist = args.recur == 'persistent'
     T, H = 161, 512
     bf = torch.bfloat16
     res = {'label': args.label, 'T': T, 'H': H, 'unit': 'us per step (graph replay of T steps / T)',
-           'lengths': args.lengths}
+           'lengths': args.lengths, 'recur': args.recur}
     for B in (32, 320):
         kw, Te = {}, T
         if args.lengths != 'none':
@@ -66,13 +70,25 @@ def main():
         runs = {'fwd_train': lambda: L.lstm_step_fwd(pre, whh, out, c, gates, T=T, B=B, H=H, **kw),
                 'fwd_infer': lambda: L.lstm_step_fwd(pre, whh, out, c1, None, T=T, B=B, H=H, **kw),
                 'bwd': lambda: L.lstm_step_bwd(dout, gates, c, whhT, dG, dc, T=T, B=B, H=H, **kw)}
-        if Te < T:
+        if persist:
+            ws = L.persist_workspace('cuda')
+            seq = lambda n, cc, gt: L.lstm_seq_fwd(pre, whh, out, cc, gt, T=n, B=B, H=H, ws=ws, **kw)
+            bwd = lambda n: L.lstm_seq_bwd(dout, gates, c, whhT, dG, dc, T=n, B=B, H=H, ws=ws, **kw)
+            runs = {'fwd_train': lambda: seq(T, c, gates), 'fwd_infer': lambda: seq(T, c1, None),
+                    'bwd': lambda: bwd(T)}
+            if Te < T:
+                runs.update({'fwd_train_trim': lambda: seq(Te, c, gates),
+                             'fwd_infer_trim': lambda: seq(Te, c1, None),
+                             'bwd_trim': lambda: bwd(Te)})
+        elif Te < T:
             runs.update({
                 'fwd_train_trim': lambda: L.lstm_step_fwd(pre, whh, out, c, gates, T=Te, B=B, H=H, **kw),
                 'fwd_infer_trim': lambda: L.lstm_step_fwd(pre, whh, out, c1, None, T=Te, B=B, H=H, **kw),
                 'bwd_trim': lambda: L.lstm_step_bwd(dout, gates, c, whhT, dG, dc, T=Te, B=B, H=H, **kw)})
         for k, fn in runs.items():
             res['%s_B%d' % (k, B)] = round(gtime(fn, reps=2, iters=5) / T, 2)
+        if persist:
+            L.persist_check(ws)
         if args.gemm:
             for F in (101, 1024):
                 xb = torch.randn(T * B, F, device='cuda').to(bf)

@@ -605,6 +605,28 @@ PYBIND11_MODULE(_C, m) {
     for (a.s = s0; a.s < s1; ++a.s) lstm_step_bwd_launch(a, S(st));
     check_launch("lstm_step_bwd");
   });
+  // the whole recurrence of a layer in one persistent launch (lstm_persist.hip)
+  m.def("lstm_seq_fwd", [](uintptr_t pre, uintptr_t whh, uintptr_t out, uintptr_t c,
+                           uintptr_t gates, uintptr_t ws, uintptr_t lens, int T, int B, int H,
+                           int train, uintptr_t st) {
+    lstm_seq_fwd_launch(LstmSeqFwdArgs{P<const float>(pre), P<const bf16>(whh), P<bf16>(out),
+                                       P<float>(c), P<bf16>(gates), P<int>(ws),
+                                       P<const int>(lens), T, B, H, train}, S(st));
+    check_launch("lstm_seq_fwd");
+  });
+  m.def("lstm_seq_bwd", [](uintptr_t dout, uintptr_t gates, uintptr_t c, uintptr_t whhT,
+                           uintptr_t dG, uintptr_t dc, uintptr_t ws, uintptr_t lens, int T, int B,
+                           int H, uintptr_t st) {
+    lstm_seq_bwd_launch(LstmSeqBwdArgs{P<const float>(dout), P<const bf16>(gates),
+                                       P<const float>(c), P<const bf16>(whhT), P<bf16>(dG),
+                                       P<float>(dc), P<int>(ws), P<const int>(lens), T, B, H},
+                        S(st));
+    check_launch("lstm_seq_bwd");
+  });
+  m.attr("LSTM_WS_INTS") = LSTM_WS_INTS;
+  m.attr("LSTM_WS_STATUS") = LSTM_WS_STATUS;
+  m.attr("LSTM_SEQ_MAX_H") = LSTM_SEQ_MAX_H;
+  m.attr("LSTM_SEQ_MAX_B") = LSTM_SEQ_MAX_B;
   // the layer's time-batched GEMMs (lstm_proj.hip)
   m.def("lstm_proj_fwd", [](uintptr_t xb, uintptr_t w_ih, uintptr_t bias, uintptr_t pre, int T,
                             int B, int F, int H, int ld, uintptr_t st) {

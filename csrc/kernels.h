@@ -461,6 +461,37 @@ struct LstmBwdArgs {                // of a forward that started from a zero sta
   const int* lens = nullptr;      // as the forward's; padded frames get dG[t] = 0 and dc = 0
 };
 void lstm_step_bwd_launch(const LstmBwdArgs& a, hipStream_t st);
+// the same recurrence as ONE launch for all T steps of both directions (lstm_persist.hip): W_hh
+// stays in registers, c / dc stay in LDS, and the blocks of a direction meet at a grid barrier
+// between steps.  Layouts and arithmetic are the step kernels'; no h0 / c0.  ws: LSTM_WS_INTS
+// int32 the caller owns -- the arrival counter of direction d at ws[LSTM_WS_CTR * d] (cleared by a
+// small kernel in front of every launch) and a sticky status word at ws[LSTM_WS_STATUS], nonzero
+// once a barrier wait ran out of its wall-clock budget (the results of that launch are wrong).
+constexpr int LSTM_WS_CTR = 32, LSTM_WS_STATUS = 64, LSTM_WS_INTS = 96;
+constexpr int LSTM_SEQ_MAX_H = 512, LSTM_SEQ_MAX_B = 512;
+struct LstmSeqFwdArgs {
+  const float* pre;               // [T][2][B][4H]
+  const bf16* whh;                // [2][4H][H]
+  bf16* out;                      // [T][B][2H]; also the step-to-step exchange buffer
+  float* c;                       // train: [T][2][B][H] every c_t; else unused (may be null)
+  bf16* gates;                    // train: [T][2][B][4H]; else null
+  int* ws;
+  const int* lens;                // [B] or null, the step kernels' rules
+  int T, B, H, train;
+};
+void lstm_seq_fwd_launch(const LstmSeqFwdArgs& a, hipStream_t st);
+struct LstmSeqBwdArgs {
+  const float* dout;              // [T][B][2H]
+  const bf16* gates;              // saved by either forward
+  const float* c;                 // [T][2][B][H]
+  const bf16* whhT;               // [2][H][4H]
+  bf16* dG;                       // [T][2][B][4H]; also the step-to-step exchange buffer
+  float* dc;                      // [2][B][H]: dc_prev of the last step, written once at the end
+  int* ws;
+  const int* lens;
+  int T, B, H;
+};
+void lstm_seq_bwd_launch(const LstmSeqBwdArgs& a, hipStream_t st);
 // the layer's time-batched GEMMs in the step kernels' layouts (lstm_proj.hip).  ld = F rounded up
 // to a multiple of 8; xb and w_ih have ld columns, zero in [F, ld).  Every tensor < 2^32 bytes.
 struct LstmProjArgs {

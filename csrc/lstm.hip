@@ -3,7 +3,8 @@
 // time step, both directions in the same launch (blockIdx.z; direction 1 walks t = T-1 .. 0).
 // The time-batched GEMMs (x . W_ih^T, dW, dx) are the caller's: torch.matmul, or the kernels of
 // lstm_proj.hip, which read and write these layouts.  Stream order is the only dependency
-// between steps -- no persistent kernel, no grid barrier.
+// between steps -- no persistent kernel, no grid barrier (that design, on the same layouts, is
+// lstm_persist.hip: recur='persistent').
 //
 // forward step   gates = pre[t] + h_prev . W_hh^T   (i, f, g, o as torch orders them)
 //                c_t = f * c_prev + i * g,  h_t = o * tanh(c_t)

@@ -36,7 +36,7 @@ HIP_FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH, '-munsafe-f
 # selection the GPU tests of those kernels were run with (not timed against packed selection)
 _NO_PK = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 EXTRA_FLAGS = {'lstm_proj.hip': _NO_PK, 'pool_wave.hip': _NO_PK, 'pool_mel.hip': _NO_PK,
-               'fc_head.hip': _NO_PK}
+               'fc_head.hip': _NO_PK, 'lstm_persist.hip': _NO_PK}
 
 
 def _pybind_includes():

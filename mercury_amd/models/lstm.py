@@ -20,6 +20,12 @@ parameters are the ``nn.LSTM`` modules' own in every case.
 It reaches only layers that take the native cell; ``cell='torch'`` with ``proj='native'`` is a
 ``ValueError``.
 
+``recur`` picks how the native cell's sequential part runs (``ops.lstm.bilstm``'s ``recur``):
+``'step'`` (default) one launch per time step, ``'persistent'`` one launch per layer pass with
+``W_hh`` resident on chip (``csrc/lstm_persist.hip``), ``'auto'`` that only at the (batch, hidden)
+sizes in ``ops.lstm.MEASURED_PERSISTENT``.  It reaches only layers that take the native cell;
+``cell='torch'`` with ``recur='persistent'`` is a ``ValueError``.
+
 ``attn`` picks how the two attention poolings run, in the same three values (``Attention``'s
 ``impl``): the eager torch chain (default), the HIP kernels of ``csrc/attn.hip``, or those only at
 the shapes where they were measured not slower (``ops.attention.MEASURED_NATIVE``).
@@ -111,7 +117,8 @@ class Attention(nn.Module):
 
 class MyLSTM(nn.Module):
     def __init__(self, feature_dim, num_classes, hidden_dim=512, lstm_layer=2, dropout=0.2,
-                 cell='torch', attn='torch', packed=False, proj='torch', head='torch'):
+                 cell='torch', attn='torch', packed=False, proj='torch', head='torch',
+                 recur='step'):
         super().__init__()
         if cell not in ('torch', 'native', 'auto'):
             raise ValueError("cell must be 'torch', 'native' or 'auto', got %r" % (cell,))
@@ -121,6 +128,10 @@ class MyLSTM(nn.Module):
             raise ValueError("proj must be 'torch', 'native' or 'auto', got %r" % (proj,))
         if head not in _IMPLS:
             raise ValueError("head must be 'torch', 'native' or 'auto', got %r" % (head,))
+        if recur not in ('step', 'persistent', 'auto'):
+            raise ValueError("recur must be 'step', 'persistent' or 'auto', got %r" % (recur,))
+        if recur == 'persistent' and cell == 'torch':
+            raise ValueError("recur='persistent' needs the native cell: cell='native' or 'auto'")
         if proj == 'native' and cell == 'torch':
             raise ValueError("proj='native' needs the native cell: cell='native' or 'auto'")
         if not isinstance(packed, bool):
@@ -130,6 +141,7 @@ class MyLSTM(nn.Module):
         self.packed = packed
         self.proj = proj
         self.head = head
+        self.recur = recur
         self.dropout = nn.Dropout(p=dropout)
         self.lstm1 = nn.LSTM(feature_dim, hidden_dim, num_layers=1, bidirectional=True)
         self.atten1 = Attention(hidden_dim * 2, batch_first=True, impl=attn)
@@ -164,11 +176,11 @@ class MyLSTM(nn.Module):
                 raise NotImplementedError("MyLSTM(packed=True, cell='native'): the native LSTM "
                                           "cell takes lengths only on a HIP device; use "
                                           "cell='torch' or 'auto'")
-            return native.bilstm(x, lstm, lengths, proj=self.proj)
+            return native.bilstm(x, lstm, lengths, proj=self.proj, recur=self.recur)
         if self.cell == 'auto' and not (
                 x.is_cuda and (x.shape[1], lstm.hidden_size) in native.MEASURED_NATIVE):
             return lstm(x)[0]
-        return native.bilstm(x, lstm, proj=self.proj)
+        return native.bilstm(x, lstm, proj=self.proj, recur=self.recur)
 
     def forward(self, x, lengths=None):
         # x: [B, 1, F, T] spectrogram (or [B, F, T]) -> time-major [T, B, F]

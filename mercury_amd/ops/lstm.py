@@ -9,7 +9,10 @@ One ``nn.LSTM(bidirectional=True, num_layers=1)`` layer, time-major ``x [T][B][F
   ``[T][2][B][4H]`` layout with the bias added, read ``dG`` in place for ``dx`` (both directions
   in one accumulator) and produce ``dW_ih``, ``dW_hh`` and ``db`` from one read of ``dG``;
 * the sequential part runs in the HIP step kernels, one launch per time step with both
-  directions in it (direction 1 walks t = T-1 .. 0).
+  directions in it (direction 1 walks t = T-1 .. 0) -- or, with ``recur='persistent'``, in the
+  kernels of ``csrc/lstm_persist.hip``: one launch for all T steps of both directions, ``W_hh``
+  resident in registers, a bounded grid barrier between steps.  Same arithmetic and saved
+  layouts; the K summation order differs, so the two routes agree to rounding, not bit for bit.
 
 Precision: every GEMM operand is bf16 (x, W_ih, W_hh, h, dG), every accumulation fp32.  ``pre``
 is kept in **fp32** (the batched GEMMs take bf16 operands and give an fp32 result: products are
@@ -53,6 +56,15 @@ MEASURED_NATIVE_PACKED = frozenset()
 # layer widths (profiles/r20/lstm_proj/lstm_bench.jsonl: 0.81-0.99 of proj='torch').
 MEASURED_NATIVE_PROJ = frozenset({(32, 101, 512), (320, 101, 512), (32, 1024, 512),
                                   (320, 1024, 512)})
+
+# (B, H) at which bench/lstm_bench.py --recur persistent measured bilstm(recur='persistent') faster
+# than bilstm(recur='step') (persistent's median below step's fastest run, forward alone and
+# forward + backward, on both layer widths); bilstm(recur='auto') takes the persistent kernels
+# exactly there.  Empty: at T = 161, H = 512 the persistent route measured 1.10-1.39 of the step
+# kernels' time at B = 32 and 1.99-2.24 at B = 320 (profiles/r24/lstm_persist/lstm_bench.jsonl).
+MEASURED_PERSISTENT = frozenset()
+# The same with lengths.  Empty: no recorded run.
+MEASURED_PERSISTENT_PACKED = frozenset()
 
 _PARAMS = ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0',
            'weight_ih_l0_reverse', 'weight_hh_l0_reverse', 'bias_ih_l0_reverse',
@@ -176,6 +188,85 @@ def _require(fn, **tensors):
     for n, t in tensors.items():
         if t is None:
             raise ValueError('%s: %s is required' % (fn, n))
+
+
+_WS = {}
+
+
+def persist_workspace(device):
+    """The persistent kernels' workspace on ``device``: a small int32 tensor (two arrival
+    counters, cleared in front of every launch, and a sticky status word), allocated once per
+    device and kept, so nothing is allocated inside a capture.  Launches that share it must be
+    ordered on one stream."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise ValueError('persist_workspace: %s is not a HIP device' % (device,))
+    idx = torch.cuda.current_device() if device.index is None else device.index
+    if idx not in _WS:
+        _WS[idx] = torch.zeros(lib().LSTM_WS_INTS, dtype=torch.int32,
+                               device=torch.device('cuda', idx))
+    return _WS[idx]
+
+
+def persist_status(ws):
+    """The status word of ``ws`` (synchronises): 0, or a code left by a block whose barrier wait
+    ran out of its wall-clock budget -- the results of that launch are wrong.  It stays set until
+    the caller clears ``ws``."""
+    return int(ws[lib().LSTM_WS_STATUS].item())
+
+
+def persist_check(ws):
+    code = persist_status(ws)
+    if code:
+        raise RuntimeError('persistent LSTM: a grid-barrier wait timed out (status %#x); the '
+                           'results of that launch are wrong' % code)
+
+
+def _chk_persist(T, B, H):
+    _chk_geom(T, B, H, 0, T)
+    if H > lib().LSTM_SEQ_MAX_H or B > lib().LSTM_SEQ_MAX_B:
+        raise ValueError('persistent LSTM: B=%d H=%d beyond the resident slice and state '
+                         '(H <= %d, B <= %d)' % (B, H, lib().LSTM_SEQ_MAX_H, lib().LSTM_SEQ_MAX_B))
+    if T * 2 * B * 4 * H * 4 >= 2 ** 32:
+        raise ValueError('persistent LSTM: a tensor of T=%d B=%d H=%d has 2^32 bytes or more'
+                         % (T, B, H))
+
+
+def lstm_seq_fwd(pre, whh, out, c, gates=None, *, T, B, H, ws, lengths=None):
+    """All T forward steps of both directions in one launch (``csrc/lstm_persist.hip``); the
+    operands of ``lstm_step_fwd`` without ``h0`` / ``c0``.  ``gates`` given = training: gates and
+    ``c`` [T][2][B][H] are saved; else ``c`` [1][2][B][H] receives the final running state.
+    ``ws``: ``persist_workspace(device)``.  Never synchronises; ``persist_check(ws)`` does."""
+    _chk_persist(T, B, H)
+    _chk_lengths(lengths, B)
+    train = gates is not None
+    _require('lstm_seq_fwd', pre=pre, whh=whh, out=out, c=c, ws=ws)
+    _chk_all(((pre, torch.float32, 'pre', T * 2 * B * 4 * H),
+              (whh, torch.bfloat16, 'whh', 2 * 4 * H * H),
+              (out, torch.bfloat16, 'out', T * B * 2 * H),
+              (c, torch.float32, 'c', (T if train else 1) * 2 * B * H),
+              (gates, torch.bfloat16, 'gates', T * 2 * B * 4 * H),
+              (ws, torch.int32, 'ws', lib().LSTM_WS_INTS)))
+    lib().lstm_seq_fwd(ptr(pre), ptr(whh), ptr(out), ptr(c), ptr(gates), ptr(ws), ptr(lengths),
+                       T, B, H, int(train), stream_ptr())
+
+
+def lstm_seq_bwd(dout, gates, c, whhT, dG, dc, *, T, B, H, ws, lengths=None):
+    """All T backward steps of both directions in one launch; the operands of ``lstm_step_bwd``
+    (``dc`` is only written: the last step's dc_prev).  ``gates`` / ``c`` as either forward saved
+    them."""
+    _chk_persist(T, B, H)
+    _chk_lengths(lengths, B)
+    _require('lstm_seq_bwd', dout=dout, gates=gates, c=c, whhT=whhT, dG=dG, dc=dc, ws=ws)
+    _chk_all(((dout, torch.float32, 'dout', T * B * 2 * H),
+              (gates, torch.bfloat16, 'gates', T * 2 * B * 4 * H),
+              (c, torch.float32, 'c', T * 2 * B * H),
+              (whhT, torch.bfloat16, 'whhT', 2 * H * 4 * H),
+              (dG, torch.bfloat16, 'dG', T * 2 * B * 4 * H),
+              (dc, torch.float32, 'dc', 2 * B * H),
+              (ws, torch.int32, 'ws', lib().LSTM_WS_INTS)))
+    lib().lstm_seq_bwd(ptr(dout), ptr(gates), ptr(c), ptr(whhT), ptr(dG), ptr(dc), ptr(ws),
+                       ptr(lengths), T, B, H, stream_ptr())
 
 
 def lstm_proj_fwd(xb, w_ih, b, pre, *, T, B, F, H, ld=None):
@@ -334,17 +425,20 @@ class BiLSTMFunction(torch.autograd.Function):
     The native steps then run as ``T = steps`` on the time-major prefixes and ``out`` / ``dG``
     beyond them are zero-filled; the batched GEMMs stay on all T frames.  A third one, ``proj``
     (bool, after ``lengths`` and ``steps``, either of which may be None), sends the batched GEMMs
-    to the kernels of ``csrc/lstm_proj.hip`` (native steps only)."""
+    to the kernels of ``csrc/lstm_proj.hip`` (native steps only).  A fourth, ``persist`` (bool),
+    sends both recurrences to the one-launch kernels of ``csrc/lstm_persist.hip`` (native steps
+    only)."""
 
     @staticmethod
     def forward(ctx, native, save, x, *params):
         ctx.n_extra = len(params) - 8
-        params, (lengths, Te, proj) = params[:8], (params[8:] + (None, None, None))[:3]
+        params, (lengths, Te, proj, persist) = params[:8], (params[8:] + (None,) * 4)[:4]
         T, B, F = x.shape
         H = params[1].shape[1]
         proj = bool(proj)
-        if proj and not native:
-            raise ValueError('BiLSTMFunction: proj needs the native steps')
+        persist = bool(persist)
+        if (proj or persist) and not native:
+            raise ValueError('BiLSTMFunction: proj and persist need the native steps')
         pk = _pack(*params, proj=proj)
         save = bool(save) and any(ctx.needs_input_grad)
         dev = x.device
@@ -368,7 +462,10 @@ class BiLSTMFunction(torch.autograd.Function):
         if native:
             if Te < T:
                 out[Te:].zero_()
-            if Te > 0:
+            if Te > 0 and persist:
+                lstm_seq_fwd(pre, pk['w_hh'], out, c, gates, T=Te, B=B, H=H,
+                             ws=persist_workspace(dev), **kw)
+            elif Te > 0:
                 lstm_step_fwd(pre, pk['w_hh'], out, c, gates, T=Te, B=B, H=H, **kw)
         else:
             _steps_fwd_torch(pre, pk['w_hh'], out, c, gates, T, B, H, **kw)
@@ -377,7 +474,7 @@ class BiLSTMFunction(torch.autograd.Function):
             ctx.lengths, ctx.steps = lengths, Te
             ctx.x_dtype = x.dtype
             ctx.need_dx = ctx.needs_input_grad[2]
-            ctx.proj, ctx.F = proj, F
+            ctx.proj, ctx.F, ctx.persist = proj, F, persist
             ctx.save_for_backward(xb, pk['w_ihT'] if proj else pk['w_ih'], pk['w_hh'], pk['w_hhT'],
                                   out, gates, c)
         return out.float()
@@ -397,7 +494,11 @@ class BiLSTMFunction(torch.autograd.Function):
                 dG[Te:].zero_()
             if Te > 0:
                 dc = torch.empty(2, B, H, dtype=torch.float32, device=xb.device)
-                lstm_step_bwd(dout, gates, c, w_hhT, dG, dc, T=Te, B=B, H=H, **kw)
+                if ctx.persist:
+                    lstm_seq_bwd(dout, gates, c, w_hhT, dG, dc, T=Te, B=B, H=H,
+                                 ws=persist_workspace(xb.device), **kw)
+                else:
+                    lstm_step_bwd(dout, gates, c, w_hhT, dG, dc, T=Te, B=B, H=H, **kw)
         else:
             _steps_bwd_torch(dout, gates, c, w_hh, dG, T, B, H, **kw)
         if ctx.proj:        # (w_ih is the transposed copy here)
@@ -453,14 +554,14 @@ def _host_steps(lengths, T):
     return max(0, min(max((int(v) for v in lengths), default=0), T))
 
 
-def _apply(native, x, lstm, lengths=None, proj=False):
+def _apply(native, x, lstm, lengths=None, proj=False, persist=False):
     params = _lstm_params(lstm)
     if x.dim() != 3 or x.shape[2] != lstm.input_size:
         raise ValueError('expected x [T][B][%d], got %s' % (lstm.input_size, tuple(x.shape)))
-    tail = (True,) if proj else ()
+    tail = (bool(proj), True) if persist else (True,) if proj else ()
     if lengths is None:
-        if proj:
-            tail = (None, None, True)
+        if tail:
+            tail = (None, None) + tail
         return BiLSTMFunction.apply(native, torch.is_grad_enabled(), x, *params, *tail)
     T, B = x.shape[:2]
     steps = _host_steps(lengths, T)
@@ -483,7 +584,22 @@ def _native_proj(proj, x, lstm):
     return True
 
 
-def bilstm(x, lstm, lengths=None, proj='torch'):
+def _persistent(recur, x, lstm, lengths):
+    """Whether ``bilstm`` sends the recurrences to lstm_persist.hip; ``'persistent'`` refuses
+    here, before any launch, what the kernels refuse."""
+    if recur not in ('step', 'persistent', 'auto'):
+        raise ValueError("recur must be 'step', 'persistent' or 'auto', got %r" % (recur,))
+    if recur == 'step' or x.dim() != 3:
+        return False
+    T, B = x.shape[:2]
+    if recur == 'auto':
+        table = MEASURED_PERSISTENT if lengths is None else MEASURED_PERSISTENT_PACKED
+        return (B, lstm.hidden_size) in table
+    _chk_persist(max(T, 1), B, lstm.hidden_size)
+    return True
+
+
+def bilstm(x, lstm, lengths=None, proj='torch', recur='step'):
     """The layer's output [T][B][2H] through the HIP step kernels; differentiable in x and the
     module's parameters.  Refuses a CPU input or an unsupported hidden size (``ValueError``).
     ``lengths``: None, a list, a CPU tensor or a device tensor of B integers (no host sync for a
@@ -495,15 +611,26 @@ def bilstm(x, lstm, lengths=None, proj='torch'):
     ``'torch'`` (default): ``torch.mm``.  ``'native'``: the kernels of ``csrc/lstm_proj.hip``, with
     and without lengths; a ``ValueError`` on a shape they refuse (an empty dimension, a tensor of
     2^32 bytes or more), never a substitute.  ``'auto'``: native only at the (B, F, H) in
-    ``MEASURED_NATIVE_PROJ``."""
+    ``MEASURED_NATIVE_PROJ``.
+
+    ``recur``: how the sequential part runs.  ``'step'`` (default): one launch per time step
+    (``csrc/lstm.hip``).  ``'persistent'``: one launch per layer pass with ``W_hh`` resident
+    (``csrc/lstm_persist.hip``), with and without lengths and with either ``proj``; a
+    ``ValueError`` beyond H <= 512, B <= 512 or on a device with fewer CUs than the 2 * H / 16
+    blocks, never a switch to the step kernels.  A barrier wait that runs out of its budget leaves
+    a code that ``persist_check(persist_workspace(x.device))`` raises on.  ``'auto'``: persistent
+    only at the (B, H) in ``MEASURED_PERSISTENT`` (``MEASURED_PERSISTENT_PACKED`` with lengths)."""
     check_hidden(lstm.hidden_size)
     if not x.is_cuda or not lstm.weight_hh_l0.is_cuda:
         raise ValueError('native LSTM cell: x and the module must be on a HIP device')
-    return _apply(True, x, lstm, lengths, _native_proj(proj, x, lstm))
+    return _apply(True, x, lstm, lengths, _native_proj(proj, x, lstm),
+                  _persistent(recur, x, lstm, lengths))
 
 
 def emulate(x, lstm, lengths=None):
     """The arithmetic of ``bilstm`` in plain torch on any device (forward and, through
     autograd, the same hand-written backward): bf16 operands, fp32 accumulation, h rounded to
-    bf16 per step, dG rounded to bf16; with ``lengths``, the same masking rules."""
+    bf16 per step, dG rounded to bf16; with ``lengths``, the same masking rules.  It states the
+    arithmetic of both ``recur`` routes (they differ from it, and from each other, only in the
+    order of the fp32 sums)."""
     return _apply(False, x, lstm, lengths)
