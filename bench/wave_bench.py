@@ -11,7 +11,9 @@ identity, with shift + gain, and as the full recipe, with the launcher's own fra
 fixed numbers of them, beside ``pool_spec_kernel``'s identity on the same-sized planar bf16
 spectrogram shard; then ``pool_wave_mel_kernel`` as the identity with ``mel=80`` (80 x 161 log-mel
 pools) and ``mel=80,dct=13`` (13 x 161 MFCC pools), the first also with fixed chunk counts.  Every
-call advances the pool counter.  Interleaved, ``--runs`` times.
+call advances the pool counter.  Interleaved, ``--runs`` times.  ``--delta K [--dwin N]`` times
+the two mel recipes beside themselves with ``delta=K`` rows instead, the MFCC one also with fixed
+chunk counts (a count whose LDS need the launcher refuses is recorded as refused).
 
 ``step``: the vgg11-speech preset as ``bench.py`` builds it (a spectrogram shard, no recipe)
 against the same network fed from a synthetic int16 waveform shard through the full recipe,
@@ -80,6 +82,12 @@ def bench_pool(args):
                'mel=80 identity': WaveRecipe.parse('wave:nfft=200,hop=100,norm=-5:4,mel=80'),
                'mel=80,dct=13 identity':
                    WaveRecipe.parse('wave:nfft=200,hop=100,norm=-5:4,mel=80,dct=13')}
+    if args.delta:          # the mel and MFCC pools again with delta rows, and fixed chunk counts
+        recipes = {k: v for k, v in recipes.items() if 'mel' in k}
+        for base in ('mel=80', 'mel=80,dct=13'):
+            recipes['%s,delta=%d identity' % (base, args.delta)] = WaveRecipe.parse(
+                'wave:nfft=200,hop=100,norm=-5:4,%s,delta=%d,dwin=%d'
+                % (base, args.delta, args.dwin))
     kr = recipes['mel=80 identity'].mel_ksteps()
     mel_macs = sum(4 * (hi - lo + 1) * 16 for lo, hi in zip(kr[::2], kr[1::2]))   # per frame
     for P in (320, 32):
@@ -109,13 +117,20 @@ def bench_pool(args):
         variants = [('pool_spec_kernel identity', 0, spec), ('counter increment alone', 0, tick)]
         for name, r in recipes.items():
             sweep = {'full': (0, 2, 3, 4, 6, 11), 'mel=80 identity': (0, 3, 4, 6, 11)}
+            if args.delta:
+                sweep = {'mel=80,dct=13,delta=%d identity' % args.delta: (0, 2, 3, 4, 6, 11)}
             for chunks in sweep.get(name, (0,)):
                 variants.append(('pool_wave_%skernel %s' % ('mel_' if r.mel else '', name), chunks,
                                  wave(r, chunks)))
         for run in range(args.runs):
             for label, chunks, fn in variants:
                 ctrl.zero_()
-                us = gtime(fn, reps=16)
+                try:
+                    us = gtime(fn, reps=16)
+                except ValueError as e:         # a forced chunk count the launcher refuses
+                    emit({'bench': 'wave_pool', 'run': run, 'P': P, 'variant': label,
+                          'chunks': chunks, 'refused': str(e)}, args.out)
+                    continue
                 rec = {'bench': 'wave_pool', 'run': run, 'P': P, 'Ns': Ns, 'variant': label,
                        'chunks': chunks, 'us': round(us, 3)}
                 if 'wave' in label:     # the padded GEMM: 176 frames x 200 x (2 x 112) columns
@@ -194,6 +209,20 @@ def bench_banks(args):
                        for k in range(4))
             emit({'bench': 'mel_panel_banks', 'pitch': pitch, 'pad': pad,
                   'worst_lanes_per_bank_write': write, 'worst_lanes_per_bank_read': read}, args.out)
+    # the delta stencil's read (clamp(t + d) - w0) * pitch + r, t = tb + 4 (lane / 16) + i, r =
+    # lane % 16, on the feature panel, away from the clip's ends and against its last frame
+    for width in (16, 48, 80, 128):
+        for pad in (0, 4):
+            pitch = width + pad
+            worst = {}
+            for name, T in (('inner', 1 << 20), ('clamped', 38)):
+                worst[name] = max(
+                    worst_b32(lambda lane: min(max(tb + 4 * (lane // 16) + i + d, 0), T - 1)
+                              * pitch + lane % 16)
+                    for tb in (21, 27) for i in range(4) for d in range(-4, 5))
+            emit({'bench': 'delta_panel_banks', 'pitch': pitch, 'pad': pad,
+                  'worst_lanes_per_bank_read': worst['inner'],
+                  'worst_lanes_per_bank_read_clamped': worst['clamped']}, args.out)
 
 
 def main():
@@ -204,6 +233,8 @@ def main():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--runs', type=int, default=3)
     ap.add_argument('--ns', type=int, default=4096)
+    ap.add_argument('--delta', type=int, default=0, choices=(0, 1, 2))
+    ap.add_argument('--dwin', type=int, default=2)
     args = ap.parse_args()
     {'pool': bench_pool, 'step': bench_step, 'banks': bench_banks}[args.mode](args)
 

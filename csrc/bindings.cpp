@@ -836,7 +836,7 @@ PYBIND11_MODULE(_C, m) {
                         float log_a, float log_b, int fmask_n, int fmask_max, int tmask_n,
                         int tmask_max, float fill, int chunks, int mel, int dct,
                         uintptr_t mel_tab, long long mel_floats, uintptr_t dct_tab,
-                        long long dct_floats, std::vector<int> krange) {
+                        long long dct_floats, std::vector<int> krange, int delta, int dwin) {
     if (!std::isfinite(gain_lo) || !std::isfinite(gain_hi) || gain_hi < gain_lo ||
         !std::isfinite(fill) || !std::isfinite(log_a) || !std::isfinite(log_b) ||
         !(noise_p >= 0.f && noise_p <= 1.f) || !(vol_max >= 0.f) || !std::isfinite(vol_max))
@@ -847,8 +847,9 @@ PYBIND11_MODULE(_C, m) {
     if (krange.size() > 16)
       throw std::invalid_argument("pool_wave: krange holds at most 8 (first, last) pairs");
     const int F = n_fft / 2 + 1;
+    const int rows = (1 + std::clamp(delta, 0, 2)) * (dct > 0 ? dct : mel > 0 ? mel : F);
     PoolWaveArgs a{pool_build_args(shard, labels, ctrl, pool, pool_label, pool_index, Ns,
-                                   dct > 0 ? dct : mel > 0 ? mel : F, 1 + L / hop, Pn, batch, 0, 0, augment, shuffle, seed,
+                                   rows, 1 + L / hop, Pn, batch, 0, 0, augment, shuffle, seed,
                                    {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, 0, zero, nzero),
                    P<const void>(noise), P<const float>(tab), tab_floats, f32, L, Nn, Ln, n_fft,
                    hop, (F + 15) & ~15, shift, gain_lo, gain_hi, noise_p, vol_max, eps, log_a,
@@ -864,6 +865,8 @@ PYBIND11_MODULE(_C, m) {
     a.dct_floats = dct_floats;
     a.krange_n = (int)krange.size();
     std::copy(krange.begin(), krange.end(), a.krange);
+    a.delta = delta;
+    a.dwin = dwin;
     pool_wave_launch(a, S(st));
     check_launch("pool_wave");
   }, py::kw_only(), py::arg("shard"), py::arg("noise") = 0, py::arg("tab"),
@@ -878,7 +881,7 @@ PYBIND11_MODULE(_C, m) {
      py::arg("tmask_n") = 0, py::arg("tmask_max") = 0, py::arg("fill") = 0.f,
      py::arg("chunks") = 0, py::arg("mel") = 0, py::arg("dct") = 0, py::arg("mel_tab") = 0,
      py::arg("mel_floats") = 0, py::arg("dct_tab") = 0, py::arg("dct_floats") = 0,
-     py::arg("krange") = std::vector<int>());
+     py::arg("krange") = std::vector<int>(), py::arg("delta") = 0, py::arg("dwin") = 2);
   m.def("is_sample", [](uintptr_t losses, uintptr_t ema, uintptr_t ctrl, uintptr_t idx, uintptr_t w,
                         uintptr_t meters, int Pn, int B, int group, int importance, float alpha,
                         float ema_alpha, uint32_t seed, uintptr_t st, int alias, uintptr_t gl,

@@ -231,6 +231,13 @@ struct PoolWaveArgs {
   int krange_n;                  // values given: 2 * M16 / 16
   int panel_pitch, lm_pitch;     // (launcher) LDS pitches of the power and log-mel panels, words
   int panel_off;                 // (launcher) first LDS word of the power panel
+  // delta rows (pool_wave_mel_kernel<.., DELTA = true>): b.H = (1 + delta) * R, rows k R + r hold
+  // the k-th time difference of feature r over +-dwin frames; masks are still drawn on (R, T)
+  int delta, dwin;               // order 0..2 (needs mel), half-window N = 1..4
+  int rows;                      // (launcher) R = dct ? dct : mel
+  float dinv;                    // (launcher) 1 / (2 sum_{n <= N} n^2)
+  int feat_off, feat_pitch;      // (launcher) fp32 feature panel [window frames][R16 + 4]
+  int d1_off;                    // (launcher) first-difference panel of order 2, same pitch
 };
 // throws std::invalid_argument on a shape the kernel cannot run (never a substitute)
 void pool_wave_launch(const PoolWaveArgs& a, hipStream_t st);

@@ -39,6 +39,33 @@
 // which dct_tab's zero rows >= M cancel -- and after a barrier [frames x M16] . [M16 x C16]
 // against dct_tab, then affine, masks, store.
 // No atomics, fixed K order: launches are bit-equal and capturable.
+//
+// Delta rows (DELTA = true, WaveRecipe.delta = 1 | 2, half-window N = dwin): rows R + r and
+// 2 R + r of the pool hold a * d1[r] and a * d2[r],
+//   d1[r][t] = sum_{n <= N} n (v[r][clamp(t + n)] - v[r][clamp(t - n)]) / (2 sum n^2),
+// clamp(u) = min(max(u, 0), T - 1), d2 the same operator on d1, v the feature before the affine.
+// A difference over +-N frames crosses the lane's 4 frames, the wave's tile and the block's
+// chunk, so the features go through LDS once more and the chunk gets a frame halo:
+//   a block OWNS output frames [o0, o1), its tiles clipped to T, and computes features for the
+//   WINDOW [w0, w1) = [o0 - h, o1 + h) clipped to [0, T), h = delta * N <= 8, in whole 16-frame
+//   tiles counted from w0 (no longer a multiple of 16): at most one tile more than it owns.
+// wave_stage stages from sample w0 * hop and phases 1 to 3 walk the window's tiles as they are.
+// Instead of storing, phase 2 (no DCT) keeps ln(mel + eps) in the log-mel panel and phase 3
+// writes the coefficients into a panel of their own over the power panel, dead after phase 2:
+//   feature panel [window frames][FP], FP = R16 + 4: at 0 without DCT, at panel_off with it
+//   d1 panel (order 2) [o0 - N, o1 + N) clipped, pitch FP: over the other dead panel -- the power
+//   panel without DCT, the log-mel panel with it.
+// Phase 4, after a barrier: a lane is (row r = 16 rt + lane % 16, frames tb + i, tb = o0 + 16 ft
+// + 4 (lane / 16)), the accumulator's mapping, over (owned frame tile, row tile) pairs.  It
+// reads panel[(clamp(t +- n) - w0) * FP + r]: bank 4 (lane / 16) FP + lane % 16 + const, the
+// store pattern above, conflict-free; in a tile that touches a clip end the clamp breaks the
+// 4-frame spacing and two words can share a bank (bench/wave_bench.py banks).  Order 2 first
+// fills the d1 panel in the same mapping from its first frame, barriers, and runs the stencil
+// again on it.  Then 4 frames of the static row and of each delta row go out through mel_store4
+// (64 contiguous bytes per row).  Every output element is the same fixed sequence of fp32
+// operations on panel values that do not depend on where the window starts (an MFMA row's
+// result does not depend on its row index), so pools built with different chunk counts are
+// bit-equal.
 #include <stdexcept>
 
 #include "common.h"
@@ -50,14 +77,17 @@ namespace {
 
 constexpr int PANEL_PAD = 4;     // pitch = width + 4 = 4 (mod 16), see above
 
-// Frames tb..tb+3 of pool row `row`: y = log_a * v + log_b, fill where masked, one bf16 rounding
-// into channel 0 of the 16-byte pixel, channels 1..7 +0.
-MA_DEV void mel_store4(const PoolWaveArgs& a, const WaveSlot& s, int slot, int row, int tb,
-                       const float v[4]) {
+// Frames tb..tb+3 of pool row `row`: y = log_a * v + log_b (a delta row, DIFF: y = log_a * v, the
+// difference of an affine feature carries no offset), fill where masked (frequency bands by the
+// feature row `frow` the pool row derives from), one bf16 rounding into channel 0 of the 16-byte
+// pixel, channels 1..7 +0.
+template <bool DIFF = false>
+MA_DEV void mel_store4(const PoolWaveArgs& a, const WaveSlot& s, int slot, int row, int frow,
+                       int tb, const float v[4]) {
   const int T = a.b.W;
   const bf16 fill = f2bf(a.fill), zero = f2bf(0.f);
-  const bool rmasked = (row >= s.f0[0] && row < s.f0[0] + s.fw[0]) ||
-                       (row >= s.f0[1] && row < s.f0[1] + s.fw[1]);
+  const bool rmasked = (frow >= s.f0[0] && frow < s.f0[0] + s.fw[0]) ||
+                       (frow >= s.f0[1] && frow < s.f0[1] + s.fw[1]);
   bf16* o = a.b.pool + (((size_t)slot * a.b.H + row) * T + tb) * 8;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -66,7 +96,7 @@ MA_DEV void mel_store4(const PoolWaveArgs& a, const WaveSlot& s, int slot, int r
     const bool masked = rmasked || (tt >= s.t0[0] && tt < s.t0[0] + s.tw[0]) ||
                         (tt >= s.t0[1] && tt < s.t0[1] + s.tw[1]);
     bf16x8 px;
-    px[0] = masked ? fill : f2bf(a.log_a * v[i] + a.log_b);
+    px[0] = masked ? fill : f2bf(DIFF ? a.log_a * v[i] : a.log_a * v[i] + a.log_b);
 #pragma unroll
     for (int c = 1; c < 8; ++c) px[c] = zero;
     *(bf16x8*)(o + (size_t)i * 8) = px;
@@ -86,7 +116,24 @@ MA_DEV f32x4 panel_gemm(const float* panel, int lda, int r0, const float* tab, i
   return acc;
 }
 
-template <typename S, int NK, bool DCT>
+// d[i] = dinv * sum_{n <= N} n (x[clamp(t0 + i + n)] - x[clamp(t0 + i - n)]), i < 4, down one
+// column `x` of a panel of pitch `pitch` whose row 0 is frame p0; frames >= tend give 0 and read
+// nothing.  One fused multiply-add per n in a fixed order, then one multiply.
+MA_DEV void delta4(const float* x, int pitch, int p0, int t0, int tend, int T, int N, float dinv,
+                   float d[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int t = t0 + i;
+    float acc = 0.f;
+    if (t < tend)
+      for (int n = 1; n <= N; ++n)
+        acc = fmaf((float)n, x[(min(t + n, T - 1) - p0) * pitch] - x[(max(t - n, 0) - p0) * pitch],
+                   acc);
+    d[i] = acc * dinv;
+  }
+}
+
+template <typename S, int NK, bool DCT, bool DELTA>
 __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(PoolWaveArgs a) {
   extern __shared__ float lds[];
   const PoolBuildArgs& b = a.b;
@@ -97,12 +144,17 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(Pool
   int64_t gb;
   int t;
   const uint32_t src = pool_src(b, slot, gb, t);
-  const WaveSlot s = wave_slot_draws(a, gb, t);
+  const WaveSlot s = wave_slot_draws<DELTA>(a, gb, t);
   if (tid == 0 && blockIdx.y == 0) wave_slot_header(a, slot, src, s);
   const int ntiles = (T + 15) >> 4;
   const int tile0 = blockIdx.y * a.tiles_per_chunk;
-  const int ntile = min(a.tiles_per_chunk, ntiles - tile0);
-  wave_stage<S>(a, s, src, tile0 * 16 * a.hop, lds, tid, nthr);
+  const int nown = min(a.tiles_per_chunk, ntiles - tile0);      // owned tiles
+  // owned frames [o0, o1), window [w0, w1) in `ntile` tiles from w0 (without DELTA: the same)
+  const int o0 = tile0 * 16, o1 = min(o0 + nown * 16, T);
+  const int halo = DELTA ? a.delta * a.dwin : 0;
+  const int w0 = DELTA ? max(o0 - halo, 0) : o0;
+  const int ntile = DELTA ? (min(o1 + halo, T) - w0 + 15) >> 4 : nown;
+  wave_stage<S>(a, s, src, w0 * a.hop, lds, tid, nthr);
   __syncthreads();
 
   // ---- phase 1: DFT, table stationary, frames streaming; power into the panel
@@ -145,39 +197,105 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(Pool
     float lm[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) lm[i] = __logf(acc[i] + a.eps);
-    if (DCT) {
+    if (DCT || DELTA) {
       float* lp = lds + (ft * 16 + kq * 4) * LP + band;
 #pragma unroll
       for (int i = 0; i < 4; ++i) lp[i * LP] = lm[i];
     } else if (band < a.mel) {
-      mel_store4(a, s, slot, band, (tile0 + ft) * 16 + kq * 4, lm);
+      mel_store4(a, s, slot, band, band, (tile0 + ft) * 16 + kq * 4, lm);
     }
   }
-  if constexpr (!DCT) return;
+  if constexpr (!DCT && !DELTA) return;
   __syncthreads();
 
   // ---- phase 3: cepstral coefficients
-  const int nct = a.C16 >> 4;
-  for (int p = wave; p < nct * ntile; p += nw) {
-    const int ft = p / nct, ct = p - ft * nct;
-    const f32x4 acc = panel_gemm(lds, LP, ft * 16, a.dct_tab, a.C16, ct * 16, 0, (a.M16 >> 2) - 1,
-                                 col, kq);
-    const int coef = ct * 16 + col;
-    const float c[4] = {acc[0], acc[1], acc[2], acc[3]};
-    if (coef < a.dct) mel_store4(a, s, slot, coef, (tile0 + ft) * 16 + kq * 4, c);
+  if constexpr (DCT) {
+    const int nct = a.C16 >> 4;
+    for (int p = wave; p < nct * ntile; p += nw) {
+      const int ft = p / nct, ct = p - ft * nct;
+      const f32x4 acc = panel_gemm(lds, LP, ft * 16, a.dct_tab, a.C16, ct * 16, 0,
+                                   (a.M16 >> 2) - 1, col, kq);
+      const int coef = ct * 16 + col;
+      const float c[4] = {acc[0], acc[1], acc[2], acc[3]};
+      if (DELTA) {            // the coefficient panel, over the power panel (padding columns: 0)
+        float* cp = panel + (ft * 16 + kq * 4) * a.feat_pitch + coef;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cp[i * a.feat_pitch] = c[i];
+      } else if (coef < a.dct) {
+        mel_store4(a, s, slot, coef, coef, (tile0 + ft) * 16 + kq * 4, c);
+      }
+    }
+    if constexpr (!DELTA) return;
+    __syncthreads();
+  }
+
+  // ---- phase 4: time differences of the feature panel, static and delta rows out
+  if constexpr (DELTA) {
+    const int R = a.rows, FP = a.feat_pitch, N = a.dwin;
+    const int nrt = (R + 15) >> 4;
+    const float* feat = lds + a.feat_off;
+    float* d1p = lds + a.d1_off;
+    const int e0 = max(o0 - N, 0), e1 = min(o1 + N, T);         // frames of the d1 panel
+    if (a.delta == 2) {
+      for (int p = wave; p < nrt * ((e1 - e0 + 15) >> 4); p += nw) {
+        const int ft = p / nrt, r = (p - ft * nrt) * 16 + col;
+        const int tb = e0 + ft * 16 + kq * 4;
+        if (r >= R) continue;
+        float d[4];
+        delta4(feat + r, FP, w0, tb, e1, T, N, a.dinv, d);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (tb + i < e1) d1p[(tb + i - e0) * FP + r] = d[i];
+      }
+      __syncthreads();
+    }
+    for (int p = wave; p < nrt * nown; p += nw) {
+      const int ft = p / nrt, r = (p - ft * nrt) * 16 + col;
+      const int tb = o0 + ft * 16 + kq * 4;
+      if (r >= R || tb >= o1) continue;
+      float v[4], d[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = feat[(min(tb + i, T - 1) - w0) * FP + r];
+      mel_store4(a, s, slot, r, r, tb, v);
+      if (a.delta == 2) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) d[i] = d1p[(min(tb + i, T - 1) - e0) * FP + r];
+      } else {
+        delta4(feat + r, FP, w0, tb, o1, T, N, a.dinv, d);
+      }
+      mel_store4<true>(a, s, slot, R + r, r, tb, d);
+      if (a.delta == 2) {
+        delta4(d1p + r, FP, e0, tb, o1, T, N, a.dinv, d);
+        mel_store4<true>(a, s, slot, 2 * R + r, r, tb, d);
+      }
+    }
   }
 }
 
-template <typename S, bool DCT>
+template <typename S, bool DCT, bool DELTA>
 void launch_nk(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds, hipStream_t st) {
   const dim3 blk(threads);
+#define MEL_LAUNCH(NK) \
+  hipLaunchKernelGGL((pool_wave_mel_kernel<S, NK, DCT, DELTA>), grid, blk, lds, st, a)
   switch (nk) {
-    case 16: hipLaunchKernelGGL((pool_wave_mel_kernel<S, 16, DCT>), grid, blk, lds, st, a); break;
-    case 32: hipLaunchKernelGGL((pool_wave_mel_kernel<S, 32, DCT>), grid, blk, lds, st, a); break;
-    case 50: hipLaunchKernelGGL((pool_wave_mel_kernel<S, 50, DCT>), grid, blk, lds, st, a); break;
-    case 64: hipLaunchKernelGGL((pool_wave_mel_kernel<S, 64, DCT>), grid, blk, lds, st, a); break;
-    default: hipLaunchKernelGGL((pool_wave_mel_kernel<S, 128, DCT>), grid, blk, lds, st, a);
+    case 16: MEL_LAUNCH(16); break;
+    case 32: MEL_LAUNCH(32); break;
+    case 50: MEL_LAUNCH(50); break;
+    case 64: MEL_LAUNCH(64); break;
+    default: MEL_LAUNCH(128);
   }
+#undef MEL_LAUNCH
+}
+
+template <typename S>
+void launch_typed(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds,
+                  hipStream_t st) {
+  if (a.delta)
+    a.dct ? launch_nk<S, true, true>(a, nk, grid, threads, lds, st)
+          : launch_nk<S, false, true>(a, nk, grid, threads, lds, st);
+  else
+    a.dct ? launch_nk<S, true, false>(a, nk, grid, threads, lds, st)
+          : launch_nk<S, false, false>(a, nk, grid, threads, lds, st);
 }
 
 }  // namespace
@@ -205,24 +323,45 @@ void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st) {
       throw std::invalid_argument("pool_wave: krange steps must lie in 0..F16/4-1");
   a.panel_pitch = a.F16 + PANEL_PAD;
   a.lm_pitch = a.M16 + PANEL_PAD;
+  a.rows = a.dct ? a.dct : a.mel;
+  a.feat_pitch = (a.dct ? a.C16 : a.M16) + PANEL_PAD;
+  a.dinv = 0.f;
+  for (int n = 1; a.delta && n <= a.dwin; ++n) a.dinv += 2.f * n * n;
+  if (a.delta) a.dinv = 1.f / a.dinv;
   const int ntiles = (b.W + 15) / 16;
+  // A block that owns `tiles` tiles computes a window of one tile more (a halo of delta * dwin
+  // <= 8 frames on each side, in whole tiles from its first frame), the clip's length at most.
+  auto window = [&](int tiles) { return a.delta ? std::min(tiles + 1, ntiles) : tiles; };
+  auto d1 = [&](int tiles) {       // the d1 panel: owned frames and dwin on each side
+    return a.delta == 2 ? (long long)(16 * tiles + 2 * a.dwin) * a.feat_pitch : 0;
+  };
+  // LDS is two regions, each as long as the longest of what lies in it over the phases:
+  // [0, panel_off) the stretch, the log-mel panel and (DCT) the d1 panel; then the power panel,
+  // (DCT) the coefficient panel and (no DCT) the d1 panel.
   auto stretch = [&](int tiles) {
-    const long long lm = a.dct ? (long long)16 * tiles * a.lm_pitch : 0;
-    return std::max(wave_stretch_words(tiles, a.hop, nk), lm);
+    const int wt = window(tiles);
+    const long long lm = (a.dct || a.delta) ? (long long)16 * wt * a.lm_pitch : 0;
+    return std::max({wave_stretch_words(wt, a.hop, nk), lm, a.dct ? d1(tiles) : 0LL});
+  };
+  auto panels = [&](int tiles) {
+    const int wt = window(tiles);
+    const long long coef = (a.dct && a.delta) ? (long long)16 * wt * a.feat_pitch : 0;
+    return std::max({(long long)16 * wt * a.panel_pitch, coef, a.dct ? 0LL : d1(tiles)});
   };
   a.tiles_per_chunk = wave_tiles_per_chunk(a.chunks, b.P, ntiles, [&](int tiles) {
-    return (stretch(tiles) + (long long)16 * tiles * a.panel_pitch) * 4;
+    return (stretch(tiles) + panels(tiles)) * 4;
   });
   const int chunks = (ntiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk;   // (no empty chunk)
-  a.lds_words = (int)wave_stretch_words(a.tiles_per_chunk, a.hop, nk);
+  a.lds_words = (int)wave_stretch_words(window(a.tiles_per_chunk), a.hop, nk);
   a.panel_off = (int)stretch(a.tiles_per_chunk);
-  const size_t lds = ((size_t)a.panel_off + (size_t)16 * a.tiles_per_chunk * a.panel_pitch) * 4;
+  a.feat_off = a.dct ? a.panel_off : 0;
+  a.d1_off = a.dct ? 0 : a.panel_off;
+  const size_t lds = ((size_t)a.panel_off + (size_t)panels(a.tiles_per_chunk)) * 4;
   const int threads = 64 * std::min(a.F16 / 16, nk > 64 ? 4 : 7);
   const dim3 grid(b.P, chunks);
   if (a.f32)
-    a.dct ? launch_nk<float, true>(a, nk, grid, threads, lds, st)
-          : launch_nk<float, false>(a, nk, grid, threads, lds, st);
+    launch_typed<float>(a, nk, grid, threads, lds, st);
   else
-    a.dct ? launch_nk<int16_t, true>(a, nk, grid, threads, lds, st)
-          : launch_nk<int16_t, false>(a, nk, grid, threads, lds, st);
+    launch_typed<int16_t>(a, nk, grid, threads, lds, st);
 }
+

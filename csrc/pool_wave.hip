@@ -149,17 +149,24 @@ void pool_wave_launch(const PoolWaveArgs& a0, hipStream_t st) {
     throw std::invalid_argument("pool_wave: Ns, P and batch must be positive");
   if (a.mel < 0 || a.dct < 0 || (a.dct && !a.mel))
     throw std::invalid_argument("pool_wave: mel and dct are >= 0, dct needs mel");
+  if (a.delta < 0 || a.delta > 2)
+    throw std::invalid_argument("pool_wave: delta must be 0..2");
+  if (a.delta && (a.dwin < 1 || a.dwin > 4))
+    throw std::invalid_argument("pool_wave: dwin must be 1..4");
+  if (a.delta && !a.mel)
+    throw std::invalid_argument("pool_wave: delta needs mel (no delta rows on the linear bins)");
   const int F = W / 2 + 1, T = 1 + L / a.hop;
-  const int R = a.dct ? a.dct : a.mel ? a.mel : F;      // pool rows
-  if (b.H != R || b.W != T || a.F16 != ((F + 15) & ~15))
-    throw std::invalid_argument("pool_wave: the pool is [P][n_fft/2+1 | mel | dct][1+L/hop][8]");
+  const int R = a.dct ? a.dct : a.mel ? a.mel : F;      // feature rows; the masks' row count
+  if (b.H != (1 + a.delta) * R || b.W != T || a.F16 != ((F + 15) & ~15))
+    throw std::invalid_argument("pool_wave: the pool is [P][(1 + delta) * (n_fft/2+1 | mel | "
+                                "dct)][1+L/hop][8]");
   if (a.noise && (a.Nn < 1 || a.Ln < L))
     throw std::invalid_argument("pool_wave: the noise bank needs Nn >= 1 clips of Ln >= L samples");
   if (a.noise && (long long)a.Ln - L >= (1 << 24))
     throw std::invalid_argument("pool_wave: Ln - L must stay below 2^24");
   const long long es = a.f32 ? 4 : 2, lim = 1LL << 32;
   if ((long long)b.Ns * L * es >= lim || (a.noise && (long long)a.Nn * a.Ln * es >= lim) ||
-      (long long)b.P * R * T * 16 >= lim)
+      (long long)b.P * b.H * T * 16 >= lim)
     throw std::invalid_argument("pool_wave: every tensor must stay below 2^32 bytes");
   if (!(a.eps > 0.f))
     throw std::invalid_argument("pool_wave: eps must be positive");

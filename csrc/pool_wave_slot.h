@@ -21,6 +21,9 @@ struct WaveSlot {
   int f0[2] = {0, 0}, fw[2] = {0, 0}, t0[2] = {0, 0}, tw[2] = {0, 0};
 };
 
+// FEAT_ROWS: the frequency masks are drawn on a.rows, the R feature rows of a pool with delta
+// rows, not on the pool's row count b.H
+template <bool FEAT_ROWS = false>
 MA_DEV WaveSlot wave_slot_draws(const PoolWaveArgs& a, int64_t gb, int t) {
   const PoolBuildArgs& b = a.b;
   WaveSlot s;
@@ -42,7 +45,7 @@ MA_DEV WaveSlot wave_slot_draws(const PoolWaveArgs& a, int64_t gb, int t) {
     for (int k = 0; k < 2; ++k) {
       if (k < a.fmask_n) {
         s.fw[k] = (int)(wr[k] % (uint32_t)(a.fmask_max + 1));
-        s.f0[k] = (int)(sr[k] % (uint32_t)(b.H - s.fw[k] + 1));
+        s.f0[k] = (int)(sr[k] % (uint32_t)((FEAT_ROWS ? a.rows : b.H) - s.fw[k] + 1));
       }
       if (k < a.tmask_n) {
         s.tw[k] = (int)(wr[2 + k] % (uint32_t)(a.tmask_max + 1));

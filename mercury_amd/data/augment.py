@@ -703,6 +703,17 @@ class WaveRecipe:
     lm[t][m] D[m][j]``, ``D[m][j] = sqrt(2/M) cos(pi (m + 0.5) j / M)`` with column 0 scaled by
     ``sqrt(1/2)`` (orthonormal DCT-II), and ``y[j][t] = a c + b``.  The output has R = C, else
     M, else F rows; masks are drawn on (R, T), and a frequency mask with ``dct`` is refused.
+    ``lifter = L >= 1`` (needs ``dct``) scales column j of D by ``1 + (L/2) sin(pi j / L)``, HTK's
+    sinusoidal lifter.
+
+    With ``delta = 1 | 2`` (needs ``mel``) and half-window ``dwin = N`` (1..4), let ``v[r][t]`` be
+    the feature before the affine (``c`` or ``lm``).  ``d1[r][t] = sum_{n=1..N} n (v[r][clamp(t +
+    n)] - v[r][clamp(t - n)]) / (2 sum_{n=1..N} n^2)``, ``clamp(u) = min(max(u, 0), T - 1)``
+    (replicate padding, torchaudio's ``compute_deltas``); ``d2`` is the same operator on ``d1``.
+    The output has ``(1 + delta) R`` rows: ``y[r] = a v[r] + b``, ``y[R + r] = a d1[r]``, ``y[2R +
+    r] = a d2[r]`` (no ``b``).  Masks come last, drawn on (R, T) as without ``delta``: a time
+    band fills every row, a frequency band of row f rows f, R + f and 2R + f; the differences
+    are taken from the unmasked features.
 
     Draws, per pool slot (Philox on the image kernels' counter ``(gb, t)``, stream words
     0x5bec8..0x5becb of its own): ``s = r % (2*shift + 1) - shift``; ``gain = fma(hi - lo,
@@ -724,10 +735,13 @@ class WaveRecipe:
     fmin: float = 0.0
     fmax: Optional[float] = None                    # None: sr / 2
     dct: int = 0                                    # cepstral coefficients kept (0: log-mel)
+    delta: int = 0                                  # order of the time differences appended
+    dwin: int = 2                                   # their half-window N, frames
+    lifter: int = 0                                 # HTK sinusoidal lifter L (0: off)
 
     def __post_init__(self):
         s = object.__setattr__
-        for k in ('n_fft', 'hop', 'shift', 'mel', 'sr', 'dct'):
+        for k in ('n_fft', 'hop', 'shift', 'mel', 'sr', 'dct', 'delta', 'dwin', 'lifter'):
             s(self, k, int(getattr(self, k)))
         s(self, 'fmin', float(self.fmin))
         s(self, 'fmax', None if self.fmax is None else float(self.fmax))
@@ -771,12 +785,21 @@ class WaveRecipe:
         if self.dct and self.fmask[0] > 0:
             raise ValueError('WaveRecipe: fmask with dct (bands of cepstral coefficients) is '
                              'refused, got fmask = %r' % (self.fmask,))
+        if not 0 <= self.delta <= 2:
+            raise ValueError('WaveRecipe: delta is 0, 1 or 2, got %d' % self.delta)
+        if self.delta and not self.mel:
+            raise ValueError('WaveRecipe: delta needs mel > 0 (no delta rows on the linear bins)')
+        if not 1 <= self.dwin <= 4:
+            raise ValueError('WaveRecipe: dwin is 1..4, got %d' % self.dwin)
+        if self.lifter < 0 or (self.lifter and not self.dct):
+            raise ValueError('WaveRecipe: lifter is >= 0 and needs dct > 0, got lifter = %d, '
+                             'dct = %d' % (self.lifter, self.dct))
 
     @classmethod
     def parse(cls, spec):
         """``wave:nfft=200,hop=100,shift=1600,gain=0.8:1.2,noise=0.8x0.1,eps=1e-6,norm=-5:4,
-        fmask=2x10,tmask=2x20,fill=0,mel=80,sr=16000,fmin=0,fmax=8000,dct=13`` (the ``wave:``
-        prefix is optional here)."""
+        fmask=2x10,tmask=2x20,fill=0,mel=80,sr=16000,fmin=0,fmax=8000,dct=13,delta=2,dwin=2,
+        lifter=22`` (the ``wave:`` prefix is optional here)."""
         spec = spec.strip()
         if spec.startswith('wave:'):
             spec = spec[5:]
@@ -785,7 +808,7 @@ class WaveRecipe:
             if '=' not in item:
                 raise ValueError('WaveRecipe.parse: %r is not name=value' % item)
             k, v = (s.strip() for s in item.split('=', 1))
-            if k in ('nfft', 'hop', 'shift', 'mel', 'sr', 'dct'):
+            if k in ('nfft', 'hop', 'shift', 'mel', 'sr', 'dct', 'delta', 'dwin', 'lifter'):
                 kw['n_fft' if k == 'nfft' else k] = int(v)
             elif k in ('fmask', 'tmask', 'noise'):
                 nm = v.split('x')
@@ -828,6 +851,12 @@ class WaveRecipe:
             if self.fmax is not None:
                 out.append('fmax=%r' % self.fmax)
             out.append('dct=%d' % self.dct)
+        if self.delta:
+            out.append('delta=%d' % self.delta)
+        if self.delta or self.dwin != 2:
+            out.append('dwin=%d' % self.dwin)
+        if self.lifter:
+            out.append('lifter=%d' % self.lifter)
         return 'wave:' + ','.join(out)
 
     @property
@@ -838,8 +867,14 @@ class WaveRecipe:
 
     def out_hw(self, L):
         """(R, T): rows and frames of an L-sample clip, the network's input size.  R is ``dct``
-        if set, else ``mel`` if set, else the F = n_fft/2 + 1 bins."""
-        return self.dct or self.mel or self.n_fft // 2 + 1, 1 + L // self.hop
+        if set, else ``mel`` if set, else the F = n_fft/2 + 1 bins; with ``delta`` the output has
+        ``(1 + delta) * R`` rows."""
+        return (1 + self.delta) * self.feat_rows, 1 + L // self.hop
+
+    @property
+    def feat_rows(self):
+        """R: the rows of one feature block, on which the frequency masks are drawn."""
+        return self.dct or self.mel or self.n_fft // 2 + 1
 
     def affine(self):
         """(a, b) of ``y = a ln(power + eps) + b``."""
@@ -852,7 +887,7 @@ class WaveRecipe:
         if L <= self.n_fft // 2:
             raise ValueError('WaveRecipe: n_fft %d needs clips longer than n_fft/2, got L = %d'
                              % (self.n_fft, L))
-        F, T = self.out_hw(L)
+        F, T = self.feat_rows, self.out_hw(L)[1]
         if self.fmask[1] > F:
             raise ValueError('WaveRecipe: fmask width %d exceeds the %d rows'
                              % (self.fmask[1], F))
@@ -882,7 +917,7 @@ class WaveRecipe:
         if self.noise is not None and ru() < self.noise[0]:
             p[2:6] = [1.0, float(ri(noise_shape[0])), float(ri(noise_shape[1] - L + 1)),
                       self.noise[1] * ru()]
-        F, T = self.out_hw(L)
+        F, T = self.feat_rows, self.out_hw(L)[1]
         for base, (n, mx), size in ((6, self.fmask, F), (10, self.tmask, T)):
             for k in range(n):
                 w = ri(mx + 1)
@@ -925,13 +960,25 @@ class WaveRecipe:
         return torch.minimum(up, down).clamp_(min=0.0)
 
     def _dct_mat(self):
-        """fp64 [M][dct]: the first ``dct`` columns of the orthonormal DCT-II."""
+        """fp64 [M][dct]: the first ``dct`` columns of the orthonormal DCT-II, column j scaled by
+        the lifter ``1 + (L/2) sin(pi j / L)`` when ``lifter = L`` is set."""
         M = self.mel
         m = torch.arange(M, dtype=torch.float64).view(M, 1)
         j = torch.arange(self.dct, dtype=torch.float64).view(1, self.dct)
         D = math.sqrt(2.0 / M) * torch.cos(math.pi * (m + 0.5) * j / M)
         D[:, 0] *= math.sqrt(0.5)
+        if self.lifter:
+            D = D * (1.0 + 0.5 * self.lifter * torch.sin(math.pi * j / self.lifter))
         return D
+
+    def _deltas(self, v):
+        """fp64 [R][T] -> the time difference of the class docstring along T (replicate ends)."""
+        N, T = self.dwin, v.shape[1]
+        t = torch.arange(T)
+        d = torch.zeros_like(v)
+        for n in range(1, N + 1):
+            d += n * (v[:, (t + n).clamp(max=T - 1)] - v[:, (t - n).clamp(min=0)])
+        return d / (2.0 * sum(n * n for n in range(1, N + 1)))
 
     def mel_table(self):
         """The kernel's filter bank, fp64 -> fp32 [F16][M16], zero padding rows and columns."""
@@ -992,7 +1039,7 @@ class WaveRecipe:
             xa = xa + p[5] * f64(noise[clip, off:off + L])
         h = W // 2
         xp = torch.cat([xa[1:h + 1].flip(0), xa, xa[L - h - 1:L - 1].flip(0)])
-        F, T = self.out_hw(L)                      # (rows of the output)
+        F, T = self.feat_rows, self.out_hw(L)[1]   # (rows of one feature block)
         n = torch.arange(W, dtype=torch.float64).view(W, 1)
         k = torch.arange(W // 2 + 1, dtype=torch.float64).view(1, W // 2 + 1)
         w = 0.5 - 0.5 * torch.cos(2 * math.pi * n / W)
@@ -1004,7 +1051,10 @@ class WaveRecipe:
             y = torch.log((re * re + im * im) @ self._mel_fb() + self.eps)     # [T][M]
             if self.dct:
                 y = y @ self._dct_mat()
-            y = (a * y + b).t()                                         # [R][T]
+            d, y = y.t(), (a * y + b).t()                               # [R][T]
+            for _ in range(self.delta):             # differences of the unmasked feature: no b
+                d = self._deltas(d)
+                y = torch.cat([y, a * d])
         else:
             y = (a * torch.log(re * re + im * im + self.eps) + b).t()   # [F][T]
         f = torch.arange(F).view(F, 1)
@@ -1014,7 +1064,8 @@ class WaveRecipe:
             masked |= (f >= int(p[q])) & (f < int(p[q]) + int(p[q + 1]))
         for q in (10, 12):
             masked |= (t >= int(p[q])) & (t < int(p[q]) + int(p[q + 1]))
+        masked = masked.repeat(1 + self.delta, 1)   # a band of row f covers rows f, R + f, 2R + f
         y = torch.where(masked, torch.tensor(self.fill, dtype=torch.float64), y)
-        out = torch.zeros(F, T, 8, dtype=dtype)
+        out = torch.zeros(y.shape[0], T, 8, dtype=dtype)
         out[:, :, 0] = y.to(dtype)
         return out

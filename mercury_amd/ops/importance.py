@@ -36,7 +36,8 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
     bank [Nn][Ln] of the same dtype and a pool [P][n_fft/2+1][1+L//hop][8]
     (``pool_wave_kernel``); ``params`` is then fp32 [P][16] (``data.augment.WAVE_PARAMS``).
     With ``mel`` (and ``dct``) set the pool is [P][R][1+L//hop][8], R = ``recipe.out_hw(L)[0]``
-    log-mel bands or cepstral coefficients (``pool_wave_mel_kernel``, ``csrc/pool_mel.hip``).
+    log-mel bands or cepstral coefficients (``pool_wave_mel_kernel``, ``csrc/pool_mel.hip``),
+    followed by their first and second time differences when ``delta`` is set.
     ``augment=False`` draws the identity and still transforms.  The first build for an
     ``(n_fft, device)`` makes the DFT table (an allocation and a copy), the first for a mel
     recipe its filter-bank and DCT tables: inside a graph capture only after such a call or
@@ -155,14 +156,15 @@ def pool_wave_table(recipe, device):
     return _WAVE_TABLES[key]
 
 
-_MEL_TABLES = {}     # (n_fft, mel, sr, fmin, fmax, dct, device) -> (mel table, dct table | None,
-#                      K ranges), built once (never inside a capture)
+_MEL_TABLES = {}     # (n_fft, mel, sr, fmin, fmax, dct, lifter, device) -> (mel table, dct table
+#                      | None, K ranges), built once (never inside a capture)
 
 
 def pool_mel_tables(recipe, device):
     """``(mel_table, dct_table or None, mel_ksteps)`` of a mel recipe, the tables resident on
     ``device``."""
-    key = (recipe.n_fft, recipe.mel, recipe.sr, recipe.fmin, recipe.fmax, recipe.dct, str(device))
+    key = (recipe.n_fft, recipe.mel, recipe.sr, recipe.fmin, recipe.fmax, recipe.dct,
+           recipe.lifter, str(device))
     if key not in _MEL_TABLES:
         _MEL_TABLES[key] = (recipe.mel_table().to(device),
                             recipe.dct_table().to(device) if recipe.dct else None,
@@ -195,7 +197,7 @@ def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batc
         mtab, dtab, krange = pool_mel_tables(recipe, shard.device)
         mel = dict(mel=recipe.mel, dct=recipe.dct, mel_tab=ptr(mtab), mel_floats=mtab.numel(),
                    dct_tab=ptr(dtab), dct_floats=dtab.numel() if dtab is not None else 0,
-                   krange=krange)
+                   krange=krange, delta=recipe.delta, dwin=recipe.dwin)
     glo, ghi = recipe.gain or (1.0, 1.0)
     p, vol = recipe.noise or (0.0, 0.0)
     a, b = recipe.affine()
