@@ -14,6 +14,9 @@ pools) and ``mel=80,dct=13`` (13 x 161 MFCC pools), the first also with fixed ch
 call advances the pool counter.  Interleaved, ``--runs`` times.  ``--delta K [--dwin N]`` times
 the two mel recipes beside themselves with ``delta=K`` rows instead, the MFCC one also with fixed
 chunk counts (a count whose LDS need the launcher refuses is recorded as refused).
+``--speed LO:HI`` times the linear, ``mel=80`` and ``mel=80,dct=13,delta=2`` identity pools beside
+themselves with ``speed=LO:HI`` (the polyphase resampler of ``csrc/pool_wave_slot.h``), each with
+the launcher's own chunk count.
 
 ``step``: the vgg11-speech preset as ``bench.py`` builds it (a spectrogram shard, no recipe)
 against the same network fed from a synthetic int16 waveform shard through the full recipe,
@@ -23,7 +26,9 @@ ms/step, interleaved, ``--runs`` times.
 lane / 16]`` for a few hops -- the worst number of lanes of a wave on one of the 64 banks, by
 the bank model of ``bench/lds_swizzle_check.py`` (``worst_b32``) -- and of the mel kernel's panel
 write ``(4 (lane / 16) + i) * pitch + lane % 16`` and read ``(lane % 16) * pitch + 4 k + lane / 16``
-for the pitches F16 + pad and M16 + pad it could take.
+for the pitches F16 + pad and M16 + pad it could take; and of the resampler's reads: the source
+panel word ``((lane0 + lane) * rq >> 16) + k`` and the table word ``p(lane) * pitch + k`` for the
+pitches 32 and 33 at the rates 0.5, 0.9, 1.1 and 2.
 One JSON line per measurement, appended to ``--out`` and printed.
 """
 from __future__ import annotations
@@ -88,6 +93,15 @@ def bench_pool(args):
             recipes['%s,delta=%d identity' % (base, args.delta)] = WaveRecipe.parse(
                 'wave:nfft=200,hop=100,norm=-5:4,%s,delta=%d,dwin=%d'
                 % (base, args.delta, args.dwin))
+    if args.speed:
+        base = 'wave:nfft=200,hop=100,norm=-5:4'
+        kinds = {'identity': base, 'mel=80 identity': base + ',mel=80',
+                 'mel=80,dct=13,delta=2 identity': base + ',mel=80,dct=13,delta=2'}
+        recipes = {}
+        for k, v in kinds.items():
+            recipes[k] = WaveRecipe.parse(v)
+            recipes[(k[:-9] + ',speed=' + args.speed).lstrip(',')] = WaveRecipe.parse(
+                v + ',speed=' + args.speed)
     kr = recipes['mel=80 identity'].mel_ksteps()
     mel_macs = sum(4 * (hi - lo + 1) * 16 for lo, hi in zip(kr[::2], kr[1::2]))   # per frame
     for P in (320, 32):
@@ -117,7 +131,9 @@ def bench_pool(args):
         variants = [('pool_spec_kernel identity', 0, spec), ('counter increment alone', 0, tick)]
         for name, r in recipes.items():
             sweep = {'full': (0, 2, 3, 4, 6, 11), 'mel=80 identity': (0, 3, 4, 6, 11)}
-            if args.delta:
+            if args.speed:
+                sweep = {}
+            elif args.delta:
                 sweep = {'mel=80,dct=13,delta=%d identity' % args.delta: (0, 2, 3, 4, 6, 11)}
             for chunks in sweep.get(name, (0,)):
                 variants.append(('pool_wave_%skernel %s' % ('mel_' if r.mel else '', name), chunks,
@@ -225,6 +241,22 @@ def bench_banks(args):
                   'worst_lanes_per_bank_read_clamped': worst['clamped']}, args.out)
 
 
+    # the resampler's FIR (wave_stage_speed): lane reads source word i0(lane) + k and table word
+    # p(lane) * pitch + k, positions one stretch word apart, that is rq / 65536 source samples
+    for rate in (0.5, 0.9, 1.1, 2.0):
+        rq = int(round(rate * 65536))
+        src, tab = 0, {32: 0, 33: 0}
+        for start in range(0, 65536, 4099):         # a few sub-sample offsets of lane 0
+            for k in range(32):
+                src = max(src, worst_b32(lambda lane: ((start + lane * rq) >> 16) + k))
+                for pitch in tab:
+                    tab[pitch] = max(tab[pitch], worst_b32(
+                        lambda lane: (((start + lane * rq) & 0xffff) >> 10) * pitch + k))
+        emit({'bench': 'speed_fir_banks', 'rate': rate, 'worst_lanes_per_bank_source': src,
+              'worst_lanes_per_bank_table_pitch32': tab[32],
+              'worst_lanes_per_bank_table_pitch33': tab[33]}, args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('mode', choices=('pool', 'step', 'banks'))
@@ -235,6 +267,7 @@ def main():
     ap.add_argument('--ns', type=int, default=4096)
     ap.add_argument('--delta', type=int, default=0, choices=(0, 1, 2))
     ap.add_argument('--dwin', type=int, default=2)
+    ap.add_argument('--speed', default='', help='LO:HI, pool mode: speed perturbation on / off')
     args = ap.parse_args()
     {'pool': bench_pool, 'step': bench_step, 'banks': bench_banks}[args.mode](args)
 

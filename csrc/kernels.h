@@ -216,7 +216,7 @@ struct PoolWaveArgs {
   int tmask_n, tmask_max;        // time masks likewise
   float fill;                    // value of masked pixels, in output units (rounded to bf16 once)
   float* params;                 // optional [P][16]: shift, gain, noise_on, clip, off, vol, f0a,
-                                 //   fwa, f0b, fwb, t0a, twa, t0b, twb, 0, 0
+                                 //   fwa, f0b, fwb, t0a, twa, t0b, twb, rq - 65536, 0
   int chunks;                    // frame chunks per slot (grid.y); 0: the launcher's measured rule
   int tiles_per_chunk, lds_words;   // (filled in by the launcher)
   // log-mel / MFCC (pool_mel.hip, pool_wave_mel_kernel); mel = 0: off, b.H = F and the kernel
@@ -238,6 +238,12 @@ struct PoolWaveArgs {
   float dinv;                    // (launcher) 1 / (2 sum_{n <= N} n^2)
   int feat_off, feat_pitch;      // (launcher) fp32 feature panel [window frames][R16 + 4]
   int d1_off;                    // (launcher) first-difference panel of order 2, same pitch
+  // speed perturbation (pool_wave_slot.h, wave_stage_speed; the SPEED instantiations): the clip
+  // is resampled about its centre by a drawn 16.16 rate rq in [rq_lo, rq_hi]; rq_hi = 0: off
+  const float* speed_tab;        // [65][32] Kaiser-windowed sinc, 64 phases and the wrap row
+  long long speed_floats;
+  int rq_lo, rq_hi;              // 32768..131072 (rates 0.5..2), lo <= hi
+  int src_off, src_words;        // (launcher) fp32 source panel in LDS; the table follows it
 };
 // throws std::invalid_argument on a shape the kernel cannot run (never a substitute)
 void pool_wave_launch(const PoolWaveArgs& a, hipStream_t st);

@@ -17,6 +17,9 @@
 //                                       phase 1, so the log-mel panel of phase 3 lies over it
 //   [panel_off, + 16 tiles * PP)        power panel [frame][bin], pitch PP = F16 + 4
 //   [0, 16 tiles * LP)  (DCT only)      log-mel panel [frame][band], pitch LP = M16 + 4
+//   [panel_off, + src_words + 65 * 33)  (SPEED) the resampler's source panel and table
+//                                       (pool_wave_slot.h), over the power panel: dead once
+//                                       the stretch is staged, before phase 1 writes the power
 // Pitch.  An accumulator lane (col = lane % 16, kq = lane / 16) holds frames 4 kq + i, i < 4, of
 // column col, so store i of a wave goes to word (r0 + 4 kq + i) * PP + c0 + col: bank
 // 4 kq PP + col + const (mod 64).  The next GEMM's A operand of K step k is the word
@@ -133,7 +136,7 @@ MA_DEV void delta4(const float* x, int pitch, int p0, int t0, int tend, int T, i
   }
 }
 
-template <typename S, int NK, bool DCT, bool DELTA>
+template <typename S, int NK, bool DCT, bool DELTA, bool SPEED = false>
 __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(PoolWaveArgs a) {
   extern __shared__ float lds[];
   const PoolBuildArgs& b = a.b;
@@ -144,8 +147,8 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(Pool
   int64_t gb;
   int t;
   const uint32_t src = pool_src(b, slot, gb, t);
-  const WaveSlot s = wave_slot_draws<DELTA>(a, gb, t);
-  if (tid == 0 && blockIdx.y == 0) wave_slot_header(a, slot, src, s);
+  const WaveSlot s = wave_slot_draws<DELTA, SPEED>(a, gb, t);
+  if (tid == 0 && blockIdx.y == 0) wave_slot_header<SPEED>(a, slot, src, s);
   const int ntiles = (T + 15) >> 4;
   const int tile0 = blockIdx.y * a.tiles_per_chunk;
   const int nown = min(a.tiles_per_chunk, ntiles - tile0);      // owned tiles
@@ -154,7 +157,7 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(Pool
   const int halo = DELTA ? a.delta * a.dwin : 0;
   const int w0 = DELTA ? max(o0 - halo, 0) : o0;
   const int ntile = DELTA ? (min(o1 + halo, T) - w0 + 15) >> 4 : nown;
-  wave_stage<S>(a, s, src, w0 * a.hop, lds, tid, nthr);
+  wave_stage_slot<S, SPEED>(a, s, src, w0 * a.hop, lds, tid, nthr);
   __syncthreads();
 
   // ---- phase 1: DFT, table stationary, frames streaming; power into the panel
@@ -272,11 +275,11 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(Pool
   }
 }
 
-template <typename S, bool DCT, bool DELTA>
+template <typename S, bool DCT, bool DELTA, bool SPEED>
 void launch_nk(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds, hipStream_t st) {
   const dim3 blk(threads);
 #define MEL_LAUNCH(NK) \
-  hipLaunchKernelGGL((pool_wave_mel_kernel<S, NK, DCT, DELTA>), grid, blk, lds, st, a)
+  hipLaunchKernelGGL((pool_wave_mel_kernel<S, NK, DCT, DELTA, SPEED>), grid, blk, lds, st, a)
   switch (nk) {
     case 16: MEL_LAUNCH(16); break;
     case 32: MEL_LAUNCH(32); break;
@@ -287,15 +290,22 @@ void launch_nk(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds
 #undef MEL_LAUNCH
 }
 
+template <typename S, bool SPEED>
+void launch_stages(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds,
+                   hipStream_t st) {
+  if (a.delta)
+    a.dct ? launch_nk<S, true, true, SPEED>(a, nk, grid, threads, lds, st)
+          : launch_nk<S, false, true, SPEED>(a, nk, grid, threads, lds, st);
+  else
+    a.dct ? launch_nk<S, true, false, SPEED>(a, nk, grid, threads, lds, st)
+          : launch_nk<S, false, false, SPEED>(a, nk, grid, threads, lds, st);
+}
+
 template <typename S>
 void launch_typed(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds,
                   hipStream_t st) {
-  if (a.delta)
-    a.dct ? launch_nk<S, true, true>(a, nk, grid, threads, lds, st)
-          : launch_nk<S, false, true>(a, nk, grid, threads, lds, st);
-  else
-    a.dct ? launch_nk<S, true, false>(a, nk, grid, threads, lds, st)
-          : launch_nk<S, false, false>(a, nk, grid, threads, lds, st);
+  a.src_words ? launch_stages<S, true>(a, nk, grid, threads, lds, st)
+              : launch_stages<S, false>(a, nk, grid, threads, lds, st);
 }
 
 }  // namespace
@@ -343,10 +353,15 @@ void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st) {
     const long long lm = (a.dct || a.delta) ? (long long)16 * wt * a.lm_pitch : 0;
     return std::max({wave_stretch_words(wt, a.hop, nk), lm, a.dct ? d1(tiles) : 0LL});
   };
+  // Speed perturbation: the resampler's source panel and table lie over the power panel, dead
+  // until phase 1, and cost LDS only where they are the longest tenant of that region.
+  const bool speed = wave_speed_on(a);
   auto panels = [&](int tiles) {
     const int wt = window(tiles);
     const long long coef = (a.dct && a.delta) ? (long long)16 * wt * a.feat_pitch : 0;
-    return std::max({(long long)16 * wt * a.panel_pitch, coef, a.dct ? 0LL : d1(tiles)});
+    const long long rs =
+        speed ? wave_speed_words(wave_stretch_words(wt, a.hop, nk), a.rq_hi) : 0;
+    return std::max({(long long)16 * wt * a.panel_pitch, coef, a.dct ? 0LL : d1(tiles), rs});
   };
   a.tiles_per_chunk = wave_tiles_per_chunk(a.chunks, b.P, ntiles, [&](int tiles) {
     return (stretch(tiles) + panels(tiles)) * 4;
@@ -356,6 +371,8 @@ void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st) {
   a.panel_off = (int)stretch(a.tiles_per_chunk);
   a.feat_off = a.dct ? a.panel_off : 0;
   a.d1_off = a.dct ? 0 : a.panel_off;
+  a.src_off = a.panel_off;
+  a.src_words = speed ? (int)wave_src_words(a.lds_words, a.rq_hi) : 0;
   const size_t lds = ((size_t)a.panel_off + (size_t)panels(a.tiles_per_chunk)) * 4;
   const int threads = 64 * std::min(a.F16 / 16, nk > 64 ? 4 : 7);
   const dim3 grid(b.P, chunks);

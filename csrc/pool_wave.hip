@@ -42,6 +42,11 @@
 // off = r % (Ln - L + 1); vol = vol_max u01; masks as pool_spec_kernel; augment = 0 draws the
 // identity.  Augmented sample: xa[j] = gain * x[j - s] (0 outside the clip), then one fused
 // multiply-add fmaf(vol, noise[clip][off + j], .) when noise is on.
+//
+// SPEED = true (WaveRecipe.speed): stream word 0x5becc .x draws a resampling rate and the stretch
+// is staged through the polyphase resampler of pool_wave_slot.h, whose source panel and table
+// lie behind the stretch in LDS ([lds_words, + src_words + 65 * 33)).  SPEED = false is the
+// kernel as it was.
 #include <stdexcept>
 
 #include "common.h"
@@ -51,7 +56,7 @@
 
 namespace {
 
-template <typename S, int NK>
+template <typename S, int NK, bool SPEED = false>
 __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_kernel(PoolWaveArgs a) {
   extern __shared__ float lds[];
   const PoolBuildArgs& b = a.b;
@@ -62,12 +67,12 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_kernel(PoolWave
   int64_t gb;
   int t;
   const uint32_t src = pool_src(b, slot, gb, t);
-  const WaveSlot s = wave_slot_draws(a, gb, t);
-  if (tid == 0 && blockIdx.y == 0) wave_slot_header(a, slot, src, s);
+  const WaveSlot s = wave_slot_draws<false, SPEED>(a, gb, t);
+  if (tid == 0 && blockIdx.y == 0) wave_slot_header<SPEED>(a, slot, src, s);
   const int ntiles = (T + 15) >> 4;
   const int tile0 = blockIdx.y * a.tiles_per_chunk;
   const int ntile = min(a.tiles_per_chunk, ntiles - tile0);
-  wave_stage<S>(a, s, src, tile0 * 16 * a.hop, lds, tid, nthr);
+  wave_stage_slot<S, SPEED>(a, s, src, tile0 * 16 * a.hop, lds, tid, nthr);
   __syncthreads();
 
   // ---- table stationary, frames streaming
@@ -115,16 +120,26 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_kernel(PoolWave
   }
 }
 
-template <typename S>
-void launch_typed(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds,
-                  hipStream_t st) {
+template <typename S, bool SPEED>
+void launch_nk(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds, hipStream_t st) {
+  const dim3 blk(threads);
+#define WAVE_LAUNCH(NK) \
+  hipLaunchKernelGGL((pool_wave_kernel<S, NK, SPEED>), grid, blk, lds, st, a)
   switch (nk) {
-    case 16: hipLaunchKernelGGL((pool_wave_kernel<S, 16>), grid, dim3(threads), lds, st, a); break;
-    case 32: hipLaunchKernelGGL((pool_wave_kernel<S, 32>), grid, dim3(threads), lds, st, a); break;
-    case 50: hipLaunchKernelGGL((pool_wave_kernel<S, 50>), grid, dim3(threads), lds, st, a); break;
-    case 64: hipLaunchKernelGGL((pool_wave_kernel<S, 64>), grid, dim3(threads), lds, st, a); break;
-    default: hipLaunchKernelGGL((pool_wave_kernel<S, 128>), grid, dim3(threads), lds, st, a);
+    case 16: WAVE_LAUNCH(16); break;
+    case 32: WAVE_LAUNCH(32); break;
+    case 50: WAVE_LAUNCH(50); break;
+    case 64: WAVE_LAUNCH(64); break;
+    default: WAVE_LAUNCH(128);
   }
+#undef WAVE_LAUNCH
+}
+
+template <typename S>
+void launch_typed(const PoolWaveArgs& a, bool speed, int nk, dim3 grid, int threads, size_t lds,
+                  hipStream_t st) {
+  speed ? launch_nk<S, true>(a, nk, grid, threads, lds, st)
+        : launch_nk<S, false>(a, nk, grid, threads, lds, st);
 }
 
 }  // namespace
@@ -176,17 +191,25 @@ void pool_wave_launch(const PoolWaveArgs& a0, hipStream_t st) {
   const int nk = pool_wave_ksteps(W);
   if (a.tab_floats != (long long)4 * nk * 2 * a.F16)
     throw std::invalid_argument("pool_wave: the table holds 4*ksteps rows of 2*F16 floats");
+  const bool speed = wave_speed_on(a);
   if (a.mel) return pool_mel_launch(a, nk, st);
   const int ntiles = (T + 15) / 16;
+  // the stretch, and behind it the resampler's source panel and table
   auto words = [&](int tiles) { return wave_stretch_words(tiles, a.hop, nk); };
+  auto need = [&](int tiles) {
+    return words(tiles) + (speed ? wave_speed_words(words(tiles), a.rq_hi) : 0);
+  };
   a.tiles_per_chunk = wave_tiles_per_chunk(a.chunks, b.P, ntiles,
-                                           [&](int tiles) { return words(tiles) * 4; });
+                                           [&](int tiles) { return need(tiles) * 4; });
   const int chunks = (ntiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk;   // (no empty chunk)
   a.lds_words = (int)words(a.tiles_per_chunk);
+  a.src_off = a.lds_words;
+  a.src_words = speed ? (int)wave_src_words(a.lds_words, a.rq_hi) : 0;
+  const size_t lds = (size_t)need(a.tiles_per_chunk) * 4;
   const int waves = std::min(a.F16 / 16, nk > 64 ? 4 : 7);
   const dim3 grid(b.P, chunks);
   if (a.f32)
-    launch_typed<float>(a, nk, grid, waves * 64, (size_t)a.lds_words * 4, st);
+    launch_typed<float>(a, speed, nk, grid, waves * 64, lds, st);
   else
-    launch_typed<int16_t>(a, nk, grid, waves * 64, (size_t)a.lds_words * 4, st);
+    launch_typed<int16_t>(a, speed, nk, grid, waves * 64, lds, st);
 }

@@ -656,7 +656,25 @@ class SpecRecipe:
 
 # ---------------------------------------------------------------------- waveforms
 WAVE_PARAMS = 16     # shift, gain, noise_on, clip, off, vol, f0a, fwa, f0b, fwb, t0a, twa, t0b,
-#                      twb, 0, 0
+#                      twb, rq - 65536 (speed), 0
+SPEED_NT, SPEED_PH, SPEED_BETA = 32, 64, 8.0    # taps, phases, Kaiser beta of the resampler
+
+
+def speed_resample(xs, js, rq, table):
+    """``xs[L]`` (fp64) read at the clip positions ``js`` (int64) through ``WaveRecipe``'s
+    polyphase resampler at the 16.16 rate ``rq``: the kernel's positions bit for bit, ``table``
+    its fp32 values (``speed_table``), the arithmetic in fp64."""
+    L, NT = xs.shape[0], SPEED_NT
+    c = L >> 1
+    pos = (c << 16) + (js.long() - c) * int(rq)
+    i0, frac = pos >> 16, pos & 0xffff
+    p, mu = frac >> 10, (frac & 1023).double() / 1024
+    h = table.double()
+    w = h[p] + mu.view(-1, 1) * (h[p + 1] - h[p])                       # [n][NT]
+    idx = i0.view(-1, 1) + torch.arange(NT) - (NT // 2 - 1)
+    src = torch.where((idx >= 0) & (idx < L), xs[idx.clamp(0, L - 1)],
+                      torch.zeros((), dtype=torch.float64))
+    return (w * src).sum(1)
 
 
 def _fpair(v, name, what='(lo, hi)'):
@@ -719,7 +737,24 @@ class WaveRecipe:
     0x5bec8..0x5becb of its own): ``s = r % (2*shift + 1) - shift``; ``gain = fma(hi - lo,
     u01(r), lo)``, one rounding; noise on iff ``u01(r) < p``, then ``clip = r % Nn``, ``off = r % (Ln - L + 1)``,
     ``vol = vol_max * u01(r)``; masks as ``SpecRecipe``.  ``augment=False`` draws the identity
-    (no shift, gain 1, no noise, no masks), so evaluation still gets its spectrogram."""
+    (no shift, gain 1, no noise, no masks), so evaluation still gets its spectrogram.
+
+    ``speed = (LO, HI)``, ``0.5 <= LO <= HI <= 2`` (speed perturbation; off by default): the clip
+    is resampled about its centre by a drawn rate, tempo and pitch together, and keeps its
+    length -- what leaves the clip is lost, what enters from outside is zero.  The rate is the
+    16.16 integer ``rq = rq_lo + r.x % (rq_hi - rq_lo + 1)``, ``rq_lo = round(LO * 65536)``,
+    ``rq_hi = round(HI * 65536)``, ``r`` one more Philox word (stream 0x5becc); ``augment=False``
+    gives 65536, and ``params[14] = rq - 65536``.  Step 1 becomes ``xa[j] = gain * xs(j - s)``
+    (still 0 unless ``0 <= j - s < L``) with, for ``js = j - s`` and ``c = L >> 1``::
+
+        pos = (c << 16) + (js - c) * rq            i0 = pos >> 16     frac = pos & 0xffff
+        p = frac >> 10      mu = (frac & 1023) / 1024
+        w_k = fma(mu, h[p + 1][k] - h[p][k], h[p][k])
+        xs = sum_{k < 32} w_k x[i0 + k - 15]       (x = 0 outside [0, L), fmaf in ascending k)
+
+    ``h = speed_table()``: 64 phases (and the wrap row) of a 32-tap Kaiser (beta 8) windowed
+    sinc with cutoff ``0.45 / max(1, HI)`` cycles per source sample.  The noise bank is not
+    resampled.  A slot with ``rq = 65536`` takes ``x[js]`` itself, unfiltered."""
     n_fft: int = 200
     hop: int = 100
     shift: int = 0                                  # maximum shift in samples
@@ -738,6 +773,7 @@ class WaveRecipe:
     delta: int = 0                                  # order of the time differences appended
     dwin: int = 2                                   # their half-window N, frames
     lifter: int = 0                                 # HTK sinusoidal lifter L (0: off)
+    speed: Optional[Tuple[float, float]] = None     # (lo, hi) resampling rate (None: off)
 
     def __post_init__(self):
         s = object.__setattr__
@@ -752,6 +788,7 @@ class WaveRecipe:
         s(self, 'gain', _fpair(self.gain, 'gain'))
         s(self, 'noise', _fpair(self.noise, 'noise', '(p, vol_max)'))
         s(self, 'norm', _fpair(self.norm, 'norm', '(mean, std)'))
+        s(self, 'speed', _fpair(self.speed, 'speed'))
         if self.n_fft % 2 or not 16 <= self.n_fft <= 512:
             raise ValueError('WaveRecipe: n_fft is even, 16..512, got %d' % self.n_fft)
         if not 1 <= self.hop <= self.n_fft:
@@ -794,12 +831,15 @@ class WaveRecipe:
         if self.lifter < 0 or (self.lifter and not self.dct):
             raise ValueError('WaveRecipe: lifter is >= 0 and needs dct > 0, got lifter = %d, '
                              'dct = %d' % (self.lifter, self.dct))
+        if self.speed is not None and not 0.5 <= self.speed[0] <= self.speed[1] <= 2.0:
+            raise ValueError('WaveRecipe: speed is (lo, hi), 0.5 <= lo <= hi <= 2, got %r'
+                             % (self.speed,))
 
     @classmethod
     def parse(cls, spec):
         """``wave:nfft=200,hop=100,shift=1600,gain=0.8:1.2,noise=0.8x0.1,eps=1e-6,norm=-5:4,
         fmask=2x10,tmask=2x20,fill=0,mel=80,sr=16000,fmin=0,fmax=8000,dct=13,delta=2,dwin=2,
-        lifter=22`` (the ``wave:`` prefix is optional here)."""
+        lifter=22,speed=0.9:1.1`` (the ``wave:`` prefix is optional here)."""
         spec = spec.strip()
         if spec.startswith('wave:'):
             spec = spec[5:]
@@ -819,7 +859,7 @@ class WaveRecipe:
                 else:
                     kw[k] = (float(nm[0]), float(nm[1])) if k == 'noise' else \
                         (int(nm[0]), int(nm[1]))
-            elif k in ('gain', 'norm'):
+            elif k in ('gain', 'norm', 'speed'):
                 g = v.split(':')
                 if v in ('', 'none'):
                     kw[k] = None
@@ -857,13 +897,16 @@ class WaveRecipe:
             out.append('dwin=%d' % self.dwin)
         if self.lifter:
             out.append('lifter=%d' % self.lifter)
+        if self.speed is not None:
+            out.append('speed=%r:%r' % self.speed)
         return 'wave:' + ','.join(out)
 
     @property
     def identity(self):
         """No augmentation on: every draw is the identity whatever the random words."""
         return (self.shift == 0 and self.gain is None and self.noise is None
-                and 0 in self.fmask and 0 in self.tmask)
+                and 0 in self.fmask and 0 in self.tmask
+                and self.speed_rq() in (None, (65536, 65536)))
 
     def out_hw(self, L):
         """(R, T): rows and frames of an L-sample clip, the network's input size.  R is ``dct``
@@ -922,6 +965,9 @@ class WaveRecipe:
             for k in range(n):
                 w = ri(mx + 1)
                 p[base + 2 * k], p[base + 2 * k + 1] = float(ri(size - w + 1)), float(w)
+        if self.speed is not None:
+            lo, hi = self.speed_rq()
+            p[14] = float(lo + ri(hi - lo + 1) - 65536)
         return p
 
     def identity_params(self):
@@ -944,6 +990,29 @@ class WaveRecipe:
         tab[:W, :F] = w * torch.cos(ang)
         tab[:W, F16:F16 + F] = -w * torch.sin(ang)
         return tab.to(torch.float32)
+
+    def speed_rq(self):
+        """``(rq_lo, rq_hi)``, the 16.16 bounds of the drawn rate, or None with ``speed`` off."""
+        if self.speed is None:
+            return None
+        return int(round(self.speed[0] * 65536)), int(round(self.speed[1] * 65536))
+
+    def speed_table(self):
+        """The resampler's filter, fp64 -> fp32 ``h[PH + 1][NT]``: ``h[p][k] = 2 fc sinc(2 fc u)
+        I0(beta sqrt(1 - (u / (NT/2))^2)) / I0(beta)``, ``u = k - (NT/2 - 1) - p / PH``, zero for
+        ``|u| > NT/2``, ``fc = 0.45 / max(1, HI)``.  Row ``PH`` is row 0 one tap on, so the phase
+        interpolation never wraps.  Not renormalised (DC gain 1.00002 to 1.00004)."""
+        if self.speed is None:
+            raise ValueError('speed_table: the recipe has no speed')
+        NT, PH = SPEED_NT, SPEED_PH
+        fc = 0.45 / max(1.0, self.speed[1])
+        k = torch.arange(NT, dtype=torch.float64).view(1, NT)
+        p = torch.arange(PH + 1, dtype=torch.float64).view(PH + 1, 1)
+        u = k - (NT // 2 - 1) - p / PH
+        r = (1.0 - (u / (NT // 2)) ** 2).clamp(min=0.0).sqrt()
+        i0b = torch.special.i0(torch.tensor(SPEED_BETA, dtype=torch.float64))
+        h = 2 * fc * torch.sinc(2 * fc * u) * torch.special.i0(SPEED_BETA * r) / i0b
+        return torch.where(u.abs() > NT // 2, torch.zeros_like(h), h).to(torch.float32)
 
     def _mel_fb(self):
         """fp64 [F][M]: the triangular HTK filter bank of the class docstring."""
@@ -1030,6 +1099,10 @@ class WaveRecipe:
         s = int(p[0])
         j = torch.arange(L)
         xs = f64(x)
+        if p[14]:         # the clip at rate rq; rq = 65536 is x[js] itself, as in the kernel
+            if self.speed is None:
+                raise ValueError('reference: params has a rate but the recipe has no speed')
+            xs = speed_resample(xs, j, 65536 + int(p[14]), self.speed_table())
         xa = p[1] * torch.where((j - s >= 0) & (j - s < L), xs[(j - s).clamp(0, L - 1)],
                                 torch.zeros((), dtype=torch.float64))
         if int(p[2]):

@@ -906,6 +906,8 @@ class NativeEngine(object):
             ops.importance.pool_wave_table(self.augment, self.device)
             if self.augment.mel:
                 ops.importance.pool_mel_tables(self.augment, self.device)
+            if self.augment.speed is not None:
+                ops.importance.pool_speed_table(self.augment, self.device)
         if self.augment is not None and self.aug_params is None:
             n = SPEC_PARAMS if isinstance(self.augment, SpecRecipe) else \
                 WAVE_PARAMS if isinstance(self.augment, WaveRecipe) else \

@@ -40,8 +40,9 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
     followed by their first and second time differences when ``delta`` is set.
     ``augment=False`` draws the identity and still transforms.  The first build for an
     ``(n_fft, device)`` makes the DFT table (an allocation and a copy), the first for a mel
-    recipe its filter-bank and DCT tables: inside a graph capture only after such a call or
-    ``pool_wave_table`` / ``pool_mel_tables`` (``NativeEngine.set_shard`` makes them)."""
+    recipe its filter-bank and DCT tables, the first for a ``speed`` recipe the resampler's
+    filter table: inside a graph capture only after such a call or ``pool_wave_table`` /
+    ``pool_mel_tables`` / ``pool_speed_table`` (``NativeEngine.set_shard`` makes them)."""
     _chk(labels, torch.int64, 'labels')
     if isinstance(recipe, WaveRecipe):
         if force_augment_kernel:
@@ -172,6 +173,17 @@ def pool_mel_tables(recipe, device):
     return _MEL_TABLES[key]
 
 
+_SPEED_TABLES = {}   # (speed hi, device) -> the resampler's filter table (never inside a capture)
+
+
+def pool_speed_table(recipe, device):
+    """``WaveRecipe.speed_table`` resident on ``device``."""
+    key = (recipe.speed[1], str(device))
+    if key not in _SPEED_TABLES:
+        _SPEED_TABLES[key] = recipe.speed_table().contiguous().to(device)
+    return _SPEED_TABLES[key]
+
+
 def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, augment,
                shuffle, zero, recipe, params, chunks=0):
     if shard.dtype not in (torch.int16, torch.float32) or shard.dim() != 2:
@@ -198,6 +210,10 @@ def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batc
         mel = dict(mel=recipe.mel, dct=recipe.dct, mel_tab=ptr(mtab), mel_floats=mtab.numel(),
                    dct_tab=ptr(dtab), dct_floats=dtab.numel() if dtab is not None else 0,
                    krange=krange, delta=recipe.delta, dwin=recipe.dwin)
+    if recipe.speed is not None:
+        stab = pool_speed_table(recipe, shard.device)
+        mel.update(speed_tab=ptr(stab), speed_floats=stab.numel(),
+                   **dict(zip(('rq_lo', 'rq_hi'), recipe.speed_rq())))
     glo, ghi = recipe.gain or (1.0, 1.0)
     p, vol = recipe.noise or (0.0, 0.0)
     a, b = recipe.affine()
