@@ -16,7 +16,10 @@ the two mel recipes beside themselves with ``delta=K`` rows instead, the MFCC on
 chunk counts (a count whose LDS need the launcher refuses is recorded as refused).
 ``--speed LO:HI`` times the linear, ``mel=80`` and ``mel=80,dct=13,delta=2`` identity pools beside
 themselves with ``speed=LO:HI`` (the polyphase resampler of ``csrc/pool_wave_slot.h``), each with
-the launcher's own chunk count.
+the launcher's own chunk count.  ``--cmvn K`` times the ``mel=80``, ``mel=80,dct=13`` and
+``mel=80,dct=13,delta=2`` identity pools beside themselves with ``cmvn=K`` (two launches:
+``pool_wave_mel_kernel`` into the fp32 workspace, ``pool_cmvn_kernel`` of ``csrc/pool_cmvn.hip``
+from it into the pool).
 
 ``step``: the vgg11-speech preset as ``bench.py`` builds it (a spectrogram shard, no recipe)
 against the same network fed from a synthetic int16 waveform shard through the full recipe,
@@ -102,6 +105,13 @@ def bench_pool(args):
             recipes[k] = WaveRecipe.parse(v)
             recipes[(k[:-9] + ',speed=' + args.speed).lstrip(',')] = WaveRecipe.parse(
                 v + ',speed=' + args.speed)
+    if args.cmvn:
+        recipes = {}
+        for k in ('mel=80', 'mel=80,dct=13', 'mel=80,dct=13,delta=2'):
+            base = 'wave:nfft=200,hop=100,norm=-5:4,' + k
+            recipes[k + ' identity'] = WaveRecipe.parse(base)
+            recipes['%s,cmvn=%d' % (k, args.cmvn)] = WaveRecipe.parse(
+                '%s,cmvn=%d' % (base, args.cmvn))
     kr = recipes['mel=80 identity'].mel_ksteps()
     mel_macs = sum(4 * (hi - lo + 1) * 16 for lo, hi in zip(kr[::2], kr[1::2]))   # per frame
     for P in (320, 32):
@@ -131,7 +141,7 @@ def bench_pool(args):
         variants = [('pool_spec_kernel identity', 0, spec), ('counter increment alone', 0, tick)]
         for name, r in recipes.items():
             sweep = {'full': (0, 2, 3, 4, 6, 11), 'mel=80 identity': (0, 3, 4, 6, 11)}
-            if args.speed:
+            if args.speed or args.cmvn:
                 sweep = {}
             elif args.delta:
                 sweep = {'mel=80,dct=13,delta=%d identity' % args.delta: (0, 2, 3, 4, 6, 11)}
@@ -268,6 +278,8 @@ def main():
     ap.add_argument('--delta', type=int, default=0, choices=(0, 1, 2))
     ap.add_argument('--dwin', type=int, default=2)
     ap.add_argument('--speed', default='', help='LO:HI, pool mode: speed perturbation on / off')
+    ap.add_argument('--cmvn', type=int, default=0, choices=(0, 1, 2),
+                    help='pool mode: per-utterance CMVN on / off')
     args = ap.parse_args()
     {'pool': bench_pool, 'step': bench_step, 'banks': bench_banks}[args.mode](args)
 

@@ -837,7 +837,8 @@ PYBIND11_MODULE(_C, m) {
                         int tmask_max, float fill, int chunks, int mel, int dct,
                         uintptr_t mel_tab, long long mel_floats, uintptr_t dct_tab,
                         long long dct_floats, std::vector<int> krange, int delta, int dwin,
-                        uintptr_t speed_tab, long long speed_floats, int rq_lo, int rq_hi) {
+                        uintptr_t speed_tab, long long speed_floats, int rq_lo, int rq_hi,
+                        int cmvn, uintptr_t feat, long long feat_floats) {
     if (!std::isfinite(gain_lo) || !std::isfinite(gain_hi) || gain_hi < gain_lo ||
         !std::isfinite(fill) || !std::isfinite(log_a) || !std::isfinite(log_b) ||
         !(noise_p >= 0.f && noise_p <= 1.f) || !(vol_max >= 0.f) || !std::isfinite(vol_max))
@@ -872,6 +873,9 @@ PYBIND11_MODULE(_C, m) {
     a.speed_floats = speed_floats;
     a.rq_lo = rq_lo;
     a.rq_hi = rq_hi;
+    a.cmvn = cmvn;
+    a.feat = P<float>(feat);
+    a.feat_floats = feat_floats;
     pool_wave_launch(a, S(st));
     check_launch("pool_wave");
   }, py::kw_only(), py::arg("shard"), py::arg("noise") = 0, py::arg("tab"),
@@ -888,7 +892,8 @@ PYBIND11_MODULE(_C, m) {
      py::arg("mel_floats") = 0, py::arg("dct_tab") = 0, py::arg("dct_floats") = 0,
      py::arg("krange") = std::vector<int>(), py::arg("delta") = 0, py::arg("dwin") = 2,
      py::arg("speed_tab") = 0, py::arg("speed_floats") = 0, py::arg("rq_lo") = 0,
-     py::arg("rq_hi") = 0);
+     py::arg("rq_hi") = 0, py::arg("cmvn") = 0, py::arg("feat") = 0,
+     py::arg("feat_floats") = 0);
   m.def("is_sample", [](uintptr_t losses, uintptr_t ema, uintptr_t ctrl, uintptr_t idx, uintptr_t w,
                         uintptr_t meters, int Pn, int B, int group, int importance, float alpha,
                         float ema_alpha, uint32_t seed, uintptr_t st, int alias, uintptr_t gl,

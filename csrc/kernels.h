@@ -244,13 +244,27 @@ struct PoolWaveArgs {
   long long speed_floats;
   int rq_lo, rq_hi;              // 32768..131072 (rates 0.5..2), lo <= hi
   int src_off, src_words;        // (launcher) fp32 source panel in LDS; the table follows it
+  // per-utterance CMVN (needs mel; pool_cmvn.hip): pool_wave_mel_kernel<.., FEAT = true> stores
+  // the raw fp32 features v[r][t] into the workspace, pool_cmvn_kernel normalises each row over
+  // the clip's T frames, takes the delta rows from the normalised row and writes the pool
+  int cmvn;                      // 0: off, 1: z = v - mean, 2: z = (v - mean) / sqrt(var + floor)
+  float* feat;                   // [P][R][feat_tp] fp32 workspace, 16-byte aligned
+  long long feat_floats;
+  int feat_tp;                   // (launcher) Tp = T rounded up to 4, the workspace's row pitch
 };
+constexpr float CMVN_VAR_FLOOR = 1e-5f;   // data/augment.py's CMVN_VAR_FLOOR (the biased variance)
+constexpr int CMVN_TP_MAX = 2048;         // two fp32 LDS rows for each of 4 waves in 64 KB
 // throws std::invalid_argument on a shape the kernel cannot run (never a substitute)
 void pool_wave_launch(const PoolWaveArgs& a, hipStream_t st);
 int pool_wave_ksteps(int n_fft);   // K steps (of 4 samples) the table is padded to; 0: unsupported
 // the mel / MFCC kernel behind pool_wave_launch (a.mel > 0): the shared checks are done, nk =
 // pool_wave_ksteps(n_fft); checks the new arguments and the LDS budget, then launches
 void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st);
+// the second launch of a cmvn recipe (pool_cmvn.hip).  pool_cmvn_check fills a.feat_tp and throws
+// on a workspace or clip length the kernel cannot take; pool_mel_launch calls it before its own
+// launch, so that a refusal launches nothing, and pool_cmvn_launch right behind it
+void pool_cmvn_check(PoolWaveArgs& a);
+void pool_cmvn_launch(const PoolWaveArgs& a, hipStream_t st);
 
 struct IsSampleArgs {
   const float* losses;           // [P]

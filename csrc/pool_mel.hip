@@ -69,6 +69,16 @@
 // operations on panel values that do not depend on where the window starts (an MFMA row's
 // result does not depend on its row index), so pools built with different chunk counts are
 // bit-equal.
+//
+// Feature-out form (FEAT = true, WaveRecipe.cmvn; always with DELTA = false, also for delta > 0):
+// per-utterance CMVN needs statistics over all T frames of a row, and no block of this grid sees
+// a whole row.  So phase 2 (no DCT) or phase 3 (DCT) stores the lane's 4 consecutive frames of
+// the RAW feature -- ln(mel + eps) or the coefficient: no affine, no mask, no rounding -- as one
+// 16-byte fp32 store into the workspace feat[slot][r][Tp], Tp = T rounded up to 4 (mel_store4's
+// mapping: 64 contiguous bytes per row and 16-lane group).  Frames >= T of a row's last 4 may
+// hold anything; nobody reads them.  pool_cmvn_kernel (pool_cmvn.hip), launched right behind on
+// the same stream, normalises, takes the delta rows and writes the pool.  No halo, no window
+// DFT computed twice, and the LDS of the DELTA = false kernel.
 #include <stdexcept>
 
 #include "common.h"
@@ -106,6 +116,13 @@ MA_DEV void mel_store4(const PoolWaveArgs& a, const WaveSlot& s, int slot, int r
   }
 }
 
+// Frames tb..tb+3 (tb a multiple of 4) of raw feature row `row` into the cmvn workspace.
+MA_DEV void feat_store4(const PoolWaveArgs& a, int slot, int row, int tb, const float v[4]) {
+  if (tb >= a.b.W) return;
+  const f32x4 q = {v[0], v[1], v[2], v[3]};
+  *(f32x4*)(a.feat + ((size_t)slot * a.rows + row) * a.feat_tp + tb) = q;
+}
+
 // One 16 x 16 output tile of [rows x K] . [K x N]: A rows r0.. of an LDS panel of pitch lda, B
 // columns n0.. of a global table of pitch ldb, K steps k0..k1 (inclusive) of 4.
 MA_DEV f32x4 panel_gemm(const float* panel, int lda, int r0, const float* tab, int ldb, int n0,
@@ -136,7 +153,7 @@ MA_DEV void delta4(const float* x, int pitch, int p0, int t0, int tend, int T, i
   }
 }
 
-template <typename S, int NK, bool DCT, bool DELTA, bool SPEED = false>
+template <typename S, int NK, bool DCT, bool DELTA, bool SPEED = false, bool FEAT = false>
 __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(PoolWaveArgs a) {
   extern __shared__ float lds[];
   const PoolBuildArgs& b = a.b;
@@ -147,7 +164,7 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(Pool
   int64_t gb;
   int t;
   const uint32_t src = pool_src(b, slot, gb, t);
-  const WaveSlot s = wave_slot_draws<DELTA, SPEED>(a, gb, t);
+  const WaveSlot s = wave_slot_draws<DELTA || FEAT, SPEED>(a, gb, t);
   if (tid == 0 && blockIdx.y == 0) wave_slot_header<SPEED>(a, slot, src, s);
   const int ntiles = (T + 15) >> 4;
   const int tile0 = blockIdx.y * a.tiles_per_chunk;
@@ -205,7 +222,10 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(Pool
 #pragma unroll
       for (int i = 0; i < 4; ++i) lp[i * LP] = lm[i];
     } else if (band < a.mel) {
-      mel_store4(a, s, slot, band, band, (tile0 + ft) * 16 + kq * 4, lm);
+      if (FEAT)
+        feat_store4(a, slot, band, (tile0 + ft) * 16 + kq * 4, lm);
+      else
+        mel_store4(a, s, slot, band, band, (tile0 + ft) * 16 + kq * 4, lm);
     }
   }
   if constexpr (!DCT && !DELTA) return;
@@ -225,7 +245,10 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(Pool
 #pragma unroll
         for (int i = 0; i < 4; ++i) cp[i * a.feat_pitch] = c[i];
       } else if (coef < a.dct) {
-        mel_store4(a, s, slot, coef, coef, (tile0 + ft) * 16 + kq * 4, c);
+        if (FEAT)
+          feat_store4(a, slot, coef, (tile0 + ft) * 16 + kq * 4, c);
+        else
+          mel_store4(a, s, slot, coef, coef, (tile0 + ft) * 16 + kq * 4, c);
       }
     }
     if constexpr (!DELTA) return;
@@ -275,11 +298,11 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(Pool
   }
 }
 
-template <typename S, bool DCT, bool DELTA, bool SPEED>
+template <typename S, bool DCT, bool DELTA, bool SPEED, bool FEAT = false>
 void launch_nk(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds, hipStream_t st) {
   const dim3 blk(threads);
 #define MEL_LAUNCH(NK) \
-  hipLaunchKernelGGL((pool_wave_mel_kernel<S, NK, DCT, DELTA, SPEED>), grid, blk, lds, st, a)
+  hipLaunchKernelGGL((pool_wave_mel_kernel<S, NK, DCT, DELTA, SPEED, FEAT>), grid, blk, lds, st, a)
   switch (nk) {
     case 16: MEL_LAUNCH(16); break;
     case 32: MEL_LAUNCH(32); break;
@@ -293,7 +316,10 @@ void launch_nk(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds
 template <typename S, bool SPEED>
 void launch_stages(const PoolWaveArgs& a, int nk, dim3 grid, int threads, size_t lds,
                    hipStream_t st) {
-  if (a.delta)
+  if (a.cmvn)
+    a.dct ? launch_nk<S, true, false, SPEED, true>(a, nk, grid, threads, lds, st)
+          : launch_nk<S, false, false, SPEED, true>(a, nk, grid, threads, lds, st);
+  else if (a.delta)
     a.dct ? launch_nk<S, true, true, SPEED>(a, nk, grid, threads, lds, st)
           : launch_nk<S, false, true, SPEED>(a, nk, grid, threads, lds, st);
   else
@@ -338,19 +364,23 @@ void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st) {
   a.dinv = 0.f;
   for (int n = 1; a.delta && n <= a.dwin; ++n) a.dinv += 2.f * n * n;
   if (a.delta) a.dinv = 1.f / a.dinv;
+  if (a.cmvn) pool_cmvn_check(a);
+  // With cmvn the first launch is the DELTA = false kernel whatever a.delta is: the rows are
+  // differenced by pool_cmvn_kernel, and this kernel needs neither halo nor delta panels.
+  const int delta = a.cmvn ? 0 : a.delta;
   const int ntiles = (b.W + 15) / 16;
   // A block that owns `tiles` tiles computes a window of one tile more (a halo of delta * dwin
   // <= 8 frames on each side, in whole tiles from its first frame), the clip's length at most.
-  auto window = [&](int tiles) { return a.delta ? std::min(tiles + 1, ntiles) : tiles; };
+  auto window = [&](int tiles) { return delta ? std::min(tiles + 1, ntiles) : tiles; };
   auto d1 = [&](int tiles) {       // the d1 panel: owned frames and dwin on each side
-    return a.delta == 2 ? (long long)(16 * tiles + 2 * a.dwin) * a.feat_pitch : 0;
+    return delta == 2 ? (long long)(16 * tiles + 2 * a.dwin) * a.feat_pitch : 0;
   };
   // LDS is two regions, each as long as the longest of what lies in it over the phases:
   // [0, panel_off) the stretch, the log-mel panel and (DCT) the d1 panel; then the power panel,
   // (DCT) the coefficient panel and (no DCT) the d1 panel.
   auto stretch = [&](int tiles) {
     const int wt = window(tiles);
-    const long long lm = (a.dct || a.delta) ? (long long)16 * wt * a.lm_pitch : 0;
+    const long long lm = (a.dct || delta) ? (long long)16 * wt * a.lm_pitch : 0;
     return std::max({wave_stretch_words(wt, a.hop, nk), lm, a.dct ? d1(tiles) : 0LL});
   };
   // Speed perturbation: the resampler's source panel and table lie over the power panel, dead
@@ -358,7 +388,7 @@ void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st) {
   const bool speed = wave_speed_on(a);
   auto panels = [&](int tiles) {
     const int wt = window(tiles);
-    const long long coef = (a.dct && a.delta) ? (long long)16 * wt * a.feat_pitch : 0;
+    const long long coef = (a.dct && delta) ? (long long)16 * wt * a.feat_pitch : 0;
     const long long rs =
         speed ? wave_speed_words(wave_stretch_words(wt, a.hop, nk), a.rq_hi) : 0;
     return std::max({(long long)16 * wt * a.panel_pitch, coef, a.dct ? 0LL : d1(tiles), rs});
@@ -380,5 +410,6 @@ void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st) {
     launch_typed<float>(a, nk, grid, threads, lds, st);
   else
     launch_typed<int16_t>(a, nk, grid, threads, lds, st);
+  if (a.cmvn) pool_cmvn_launch(a, st);
 }
 

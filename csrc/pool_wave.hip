@@ -170,6 +170,10 @@ void pool_wave_launch(const PoolWaveArgs& a0, hipStream_t st) {
     throw std::invalid_argument("pool_wave: dwin must be 1..4");
   if (a.delta && !a.mel)
     throw std::invalid_argument("pool_wave: delta needs mel (no delta rows on the linear bins)");
+  if (a.cmvn < 0 || a.cmvn > 2)
+    throw std::invalid_argument("pool_wave: cmvn must be 0..2");
+  if (a.cmvn && !a.mel)
+    throw std::invalid_argument("pool_wave: cmvn needs mel (no CMVN on the linear bins)");
   const int F = W / 2 + 1, T = 1 + L / a.hop;
   const int R = a.dct ? a.dct : a.mel ? a.mel : F;      // feature rows; the masks' row count
   if (b.H != (1 + a.delta) * R || b.W != T || a.F16 != ((F + 15) & ~15))

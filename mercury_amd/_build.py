@@ -32,11 +32,11 @@ HIP_FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH, '-munsafe-f
 
 # per-source extra flags.  lstm_proj.hip: no packed-fp32 instruction selection for its epilogue
 # adds (the host pass does not know the feature and says so; that is harmless); pool_wave.hip,
-# pool_mel.hip, fc_head.hip and the diagnostic kernels likewise: new fp32 epilogues keep one instruction per value, the
+# pool_mel.hip, pool_cmvn.hip, fc_head.hip and the diagnostic kernels likewise: new fp32 epilogues keep one instruction per value, the
 # selection the GPU tests of those kernels were run with (not timed against packed selection)
 _NO_PK = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 EXTRA_FLAGS = {'lstm_proj.hip': _NO_PK, 'pool_wave.hip': _NO_PK, 'pool_mel.hip': _NO_PK,
-               'fc_head.hip': _NO_PK, 'lstm_persist.hip': _NO_PK}
+               'fc_head.hip': _NO_PK, 'lstm_persist.hip': _NO_PK, 'pool_cmvn.hip': _NO_PK}
 
 
 def _pybind_includes():

@@ -658,6 +658,7 @@ class SpecRecipe:
 WAVE_PARAMS = 16     # shift, gain, noise_on, clip, off, vol, f0a, fwa, f0b, fwb, t0a, twa, t0b,
 #                      twb, rq - 65536 (speed), 0
 SPEED_NT, SPEED_PH, SPEED_BETA = 32, 64, 8.0    # taps, phases, Kaiser beta of the resampler
+CMVN_VAR_FLOOR = 1e-5     # added to the biased variance of ``cmvn=2`` (csrc/kernels.h has its twin)
 
 
 def speed_resample(xs, js, rq, table):
@@ -754,7 +755,19 @@ class WaveRecipe:
 
     ``h = speed_table()``: 64 phases (and the wrap row) of a 32-tap Kaiser (beta 8) windowed
     sinc with cutoff ``0.45 / max(1, HI)`` cycles per source sample.  The noise bank is not
-    resampled.  A slot with ``rq = 65536`` takes ``x[js]`` itself, unfiltered."""
+    resampled.  A slot with ``rq = 65536`` takes ``x[js]`` itself, unfiltered.
+
+    ``cmvn = 1 | 2`` (needs ``mel``; off by default): cepstral mean (and variance) normalisation
+    per utterance, over the clip's T frames, of the feature ``v`` above: ``mu_r = mean_t
+    v[r][t]``, ``var_r = mean_t (v[r][t] - mu_r)^2`` (the biased variance, as Kaldi's
+    ``apply-cmvn`` takes it), ``z = v - mu_r`` for ``cmvn=1`` and ``z = (v - mu_r) / sqrt(var_r +
+    CMVN_VAR_FLOOR)`` for ``cmvn=2``.  Then ``y[r] = a z + b``, and the delta rows are the
+    difference operator on ``z`` (no ``b``).  The statistics come from the unmasked fp32 features
+    (``pool_cmvn_kernel``, ``csrc/pool_cmvn.hip``); masks still come last.  T = 1 gives ``z = 0``.
+
+    ``preemph = C``, ``0 <= C < 1`` (off by default): Kaldi's per-frame pre-emphasis of each
+    frame ``f[0..W)`` of the padded signal before the window, ``s[0] = f[0] - C f[0]``, ``s[n] =
+    f[n] - C f[n-1]``.  It is linear in the frame, so it lives in ``table()`` alone."""
     n_fft: int = 200
     hop: int = 100
     shift: int = 0                                  # maximum shift in samples
@@ -774,11 +787,14 @@ class WaveRecipe:
     dwin: int = 2                                   # their half-window N, frames
     lifter: int = 0                                 # HTK sinusoidal lifter L (0: off)
     speed: Optional[Tuple[float, float]] = None     # (lo, hi) resampling rate (None: off)
+    cmvn: int = 0                                   # 1: mean, 2: mean and variance, per clip
+    preemph: float = 0.0                            # pre-emphasis coefficient C (0: off)
 
     def __post_init__(self):
         s = object.__setattr__
-        for k in ('n_fft', 'hop', 'shift', 'mel', 'sr', 'dct', 'delta', 'dwin', 'lifter'):
+        for k in ('n_fft', 'hop', 'shift', 'mel', 'sr', 'dct', 'delta', 'dwin', 'lifter', 'cmvn'):
             s(self, k, int(getattr(self, k)))
+        s(self, 'preemph', float(self.preemph))
         s(self, 'fmin', float(self.fmin))
         s(self, 'fmax', None if self.fmax is None else float(self.fmax))
         s(self, 'fmask', _mask(self.fmask, 'fmask'))
@@ -834,12 +850,18 @@ class WaveRecipe:
         if self.speed is not None and not 0.5 <= self.speed[0] <= self.speed[1] <= 2.0:
             raise ValueError('WaveRecipe: speed is (lo, hi), 0.5 <= lo <= hi <= 2, got %r'
                              % (self.speed,))
+        if not 0 <= self.cmvn <= 2:
+            raise ValueError('WaveRecipe: cmvn is 0, 1 or 2, got %d' % self.cmvn)
+        if self.cmvn and not self.mel:
+            raise ValueError('WaveRecipe: cmvn needs mel > 0 (no CMVN on the linear bins)')
+        if not 0 <= self.preemph < 1:
+            raise ValueError('WaveRecipe: preemph is 0 <= C < 1, got %r' % self.preemph)
 
     @classmethod
     def parse(cls, spec):
         """``wave:nfft=200,hop=100,shift=1600,gain=0.8:1.2,noise=0.8x0.1,eps=1e-6,norm=-5:4,
         fmask=2x10,tmask=2x20,fill=0,mel=80,sr=16000,fmin=0,fmax=8000,dct=13,delta=2,dwin=2,
-        lifter=22,speed=0.9:1.1`` (the ``wave:`` prefix is optional here)."""
+        lifter=22,speed=0.9:1.1,cmvn=2,preemph=0.97`` (the ``wave:`` prefix is optional here)."""
         spec = spec.strip()
         if spec.startswith('wave:'):
             spec = spec[5:]
@@ -848,7 +870,8 @@ class WaveRecipe:
             if '=' not in item:
                 raise ValueError('WaveRecipe.parse: %r is not name=value' % item)
             k, v = (s.strip() for s in item.split('=', 1))
-            if k in ('nfft', 'hop', 'shift', 'mel', 'sr', 'dct', 'delta', 'dwin', 'lifter'):
+            if k in ('nfft', 'hop', 'shift', 'mel', 'sr', 'dct', 'delta', 'dwin', 'lifter',
+                     'cmvn'):
                 kw['n_fft' if k == 'nfft' else k] = int(v)
             elif k in ('fmask', 'tmask', 'noise'):
                 nm = v.split('x')
@@ -867,7 +890,7 @@ class WaveRecipe:
                     raise ValueError('WaveRecipe.parse: %s is A:B, got %r' % (k, v))
                 else:
                     kw[k] = (float(g[0]), float(g[1]))
-            elif k in ('fill', 'eps', 'fmin'):
+            elif k in ('fill', 'eps', 'fmin', 'preemph'):
                 kw[k] = float(v)
             elif k == 'fmax':
                 kw[k] = None if v in ('', 'none') else float(v)
@@ -899,6 +922,10 @@ class WaveRecipe:
             out.append('lifter=%d' % self.lifter)
         if self.speed is not None:
             out.append('speed=%r:%r' % self.speed)
+        if self.cmvn:
+            out.append('cmvn=%d' % self.cmvn)
+        if self.preemph:
+            out.append('preemph=%r' % self.preemph)
         return 'wave:' + ','.join(out)
 
     @property
@@ -978,7 +1005,10 @@ class WaveRecipe:
     def table(self, ksteps=None):
         """The window-folded DFT table of the kernel, fp64 -> fp32 [4*ksteps][2*F16]: columns
         ``[0, F)`` hold ``w[n] cos(2 pi k n / W)``, columns ``[F16, F16 + F)`` hold
-        ``-w[n] sin(2 pi k n / W)``; rows ``>= W`` and the padding columns are zero."""
+        ``-w[n] sin(2 pi k n / W)``; rows ``>= W`` and the padding columns are zero.  With
+        ``preemph = C`` row ``n <= W - 2`` is ``w[n] E[n] - C w[n+1] E[n+1]`` (``E`` the cos / -sin
+        pair), row ``W - 1`` stays and row 0 loses ``C w[0] E[0]`` as well: the DFT of the
+        pre-emphasised frame as one product with the frame itself, folded in fp64."""
         W, F = self.n_fft, self.n_fft // 2 + 1
         F16 = (F + 15) // 16 * 16
         rows = 4 * ksteps if ksteps else W
@@ -989,6 +1019,10 @@ class WaveRecipe:
         tab = torch.zeros(rows, 2 * F16, dtype=torch.float64)
         tab[:W, :F] = w * torch.cos(ang)
         tab[:W, F16:F16 + F] = -w * torch.sin(ang)
+        if self.preemph:
+            first = tab[0].clone()
+            tab[:W - 1] -= self.preemph * tab[1:W].clone()
+            tab[0] -= self.preemph * first
         return tab.to(torch.float32)
 
     def speed_rq(self):
@@ -1118,12 +1152,18 @@ class WaveRecipe:
         w = 0.5 - 0.5 * torch.cos(2 * math.pi * n / W)
         ang = 2 * math.pi * ((n * k) % W) / W
         frames = xp.unfold(0, W, hop)[:T]                               # [T][W]
+        if self.preemph:
+            frames = frames - self.preemph * torch.cat([frames[:, :1], frames[:, :-1]], 1)
         re, im = frames @ (w * torch.cos(ang)), frames @ (-w * torch.sin(ang))
         a, b = self.affine()
         if self.mel:
             y = torch.log((re * re + im * im) @ self._mel_fb() + self.eps)     # [T][M]
             if self.dct:
                 y = y @ self._dct_mat()
+            if self.cmvn:                           # per row over the clip's frames
+                y = y - y.mean(0, keepdim=True)
+                if self.cmvn == 2:
+                    y = y / (y * y).mean(0, keepdim=True).add(CMVN_VAR_FLOOR).sqrt()
             d, y = y.t(), (a * y + b).t()                               # [R][T]
             for _ in range(self.delta):             # differences of the unmasked feature: no b
                 d = self._deltas(d)

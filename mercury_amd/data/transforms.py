@@ -296,7 +296,8 @@ class SpecAugment(object):
 class WaveSpectrogram(object):
     """A ``WaveRecipe`` (``data/augment.py``: shift, gain and background noise on the raw clip,
     then the log-spectrogram, or with ``mel`` / ``dct`` set the log-mel bands or cepstral
-    coefficients) on one waveform [L] (int16 PCM or float) -> float32 [1][R][T], (R, T) =
+    coefficients, with ``preemph`` pre-emphasised frames and with ``cmvn`` each row normalised
+    over the clip) on one waveform [L] (int16 PCM or float) -> float32 [1][R][T], (R, T) =
     ``recipe.out_hw(L)``.
     The draws come from torch's RNG (``generator``) through ``WaveRecipe.draw``, the arithmetic
     is ``WaveRecipe.reference``; ``noise`` is the bank [Nn][Ln] a ``noise=`` recipe mixes from,

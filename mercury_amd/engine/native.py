@@ -908,6 +908,9 @@ class NativeEngine(object):
                 ops.importance.pool_mel_tables(self.augment, self.device)
             if self.augment.speed is not None:
                 ops.importance.pool_speed_table(self.augment, self.device)
+            if self.augment.cmvn:                    # the pool's and the plain batch's workspace
+                for n in (self.P, self.B):
+                    ops.importance.pool_cmvn_workspace(self.augment, n, x.shape[1], self.device)
         if self.augment is not None and self.aug_params is None:
             n = SPEC_PARAMS if isinstance(self.augment, SpecRecipe) else \
                 WAVE_PARAMS if isinstance(self.augment, WaveRecipe) else \

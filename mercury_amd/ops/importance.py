@@ -41,8 +41,11 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
     ``augment=False`` draws the identity and still transforms.  The first build for an
     ``(n_fft, device)`` makes the DFT table (an allocation and a copy), the first for a mel
     recipe its filter-bank and DCT tables, the first for a ``speed`` recipe the resampler's
-    filter table: inside a graph capture only after such a call or ``pool_wave_table`` /
-    ``pool_mel_tables`` / ``pool_speed_table`` (``NativeEngine.set_shard`` makes them)."""
+    filter table, the first for a ``cmvn`` recipe and pool shape its fp32 feature workspace (the
+    recipe then runs two launches: ``pool_wave_mel_kernel`` into the workspace, ``pool_cmvn_kernel``
+    from it into the pool): inside a graph capture only after such a call or ``pool_wave_table`` /
+    ``pool_mel_tables`` / ``pool_speed_table`` / ``pool_cmvn_workspace``
+    (``NativeEngine.set_shard`` makes them).  ``preemph`` only changes the DFT table."""
     _chk(labels, torch.int64, 'labels')
     if isinstance(recipe, WaveRecipe):
         if force_augment_kernel:
@@ -146,12 +149,12 @@ def _pool_spec(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
                     ptr(params), chunks)
 
 
-_WAVE_TABLES = {}    # (n_fft, device) -> the DFT table, built once (never inside a capture)
+_WAVE_TABLES = {}    # (n_fft, preemph, device) -> the DFT table, built once (never inside a capture)
 
 
 def pool_wave_table(recipe, device):
     """``WaveRecipe.table`` padded to the kernel's K steps, resident on ``device``."""
-    key = (recipe.n_fft, str(device))
+    key = (recipe.n_fft, recipe.preemph, str(device))
     if key not in _WAVE_TABLES:
         _WAVE_TABLES[key] = recipe.table(lib().pool_wave_ksteps(recipe.n_fft)).to(device)
     return _WAVE_TABLES[key]
@@ -184,6 +187,21 @@ def pool_speed_table(recipe, device):
     return _SPEED_TABLES[key]
 
 
+_CMVN_FEAT = {}      # (P, R, Tp, device) -> the fp32 feature workspace of a cmvn recipe
+
+
+def pool_cmvn_workspace(recipe, P, L, device):
+    """The fp32 workspace ``[P][R][Tp]``, ``Tp = T`` rounded up to 4, through which a ``cmvn``
+    recipe's two launches hand the raw features, one per shape and device (never allocated
+    inside a capture: ``NativeEngine.set_shard`` makes it).  Pool builds of one shape share it,
+    which is safe on one stream, where the launches are ordered."""
+    R, T = recipe.feat_rows, recipe.out_hw(L)[1]
+    key = (P, R, (T + 3) // 4 * 4, str(device))
+    if key not in _CMVN_FEAT:
+        _CMVN_FEAT[key] = torch.empty(key[:3], dtype=torch.float32, device=device)
+    return _CMVN_FEAT[key]
+
+
 def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, augment,
                shuffle, zero, recipe, params, chunks=0):
     if shard.dtype not in (torch.int16, torch.float32) or shard.dim() != 2:
@@ -214,6 +232,9 @@ def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batc
         stab = pool_speed_table(recipe, shard.device)
         mel.update(speed_tab=ptr(stab), speed_floats=stab.numel(),
                    **dict(zip(('rq_lo', 'rq_hi'), recipe.speed_rq())))
+    if recipe.cmvn:
+        feat = pool_cmvn_workspace(recipe, P, L, shard.device)
+        mel.update(cmvn=recipe.cmvn, feat=ptr(feat), feat_floats=feat.numel())
     glo, ghi = recipe.gain or (1.0, 1.0)
     p, vol = recipe.noise or (0.0, 0.0)
     a, b = recipe.affine()
