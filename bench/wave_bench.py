@@ -19,7 +19,11 @@ themselves with ``speed=LO:HI`` (the polyphase resampler of ``csrc/pool_wave_slo
 the launcher's own chunk count.  ``--cmvn K`` times the ``mel=80``, ``mel=80,dct=13`` and
 ``mel=80,dct=13,delta=2`` identity pools beside themselves with ``cmvn=K`` (two launches:
 ``pool_wave_mel_kernel`` into the fp32 workspace, ``pool_cmvn_kernel`` of ``csrc/pool_cmvn.hip``
-from it into the pool).
+from it into the pool).  ``--reverb P --rir-taps K`` times the linear and ``mel=80,dct=13,delta=2``
+identity pools beside themselves with ``reverb=P`` on a bank of 8 K-tap responses
+(``pool_reverb_kernel`` of ``csrc/pool_reverb.hip`` in front), the launcher's pre-pass chunk count
+and a few forced ones; ``gflop_reverb`` is the padded GEMM ``P * 2 * 16128 * (K16 + 16)`` of the
+slots that drew reverb on (all of them at P = 1).
 
 ``step``: the vgg11-speech preset as ``bench.py`` builds it (a spectrogram shard, no recipe)
 against the same network fed from a synthetic int16 waveform shard through the full recipe,
@@ -31,7 +35,9 @@ the bank model of ``bench/lds_swizzle_check.py`` (``worst_b32``) -- and of the m
 write ``(4 (lane / 16) + i) * pitch + lane % 16`` and read ``(lane % 16) * pitch + 4 k + lane / 16``
 for the pitches F16 + pad and M16 + pad it could take; and of the resampler's reads: the source
 panel word ``((lane0 + lane) * rq >> 16) + k`` and the table word ``p(lane) * pitch + k`` for the
-pitches 32 and 33 at the rates 0.5, 0.9, 1.1 and 2.
+pitches 32 and 33 at the rates 0.5, 0.9, 1.1 and 2; and of the reverb pre-pass's clip read
+``w + pad (w >> 4)``, ``w = 16 (lane % 16) + 15 - 4 si - lane / 16``, for 0, 1 and 4 pad words per
+16, and its response read ``4 si + lane / 16 + lane % 16``.
 One JSON line per measurement, appended to ``--out`` and printed.
 """
 from __future__ import annotations
@@ -112,7 +118,19 @@ def bench_pool(args):
             recipes[k + ' identity'] = WaveRecipe.parse(base)
             recipes['%s,cmvn=%d' % (k, args.cmvn)] = WaveRecipe.parse(
                 '%s,cmvn=%d' % (base, args.cmvn))
-    kr = recipes['mel=80 identity'].mel_ksteps()
+    rir = None
+    if args.reverb:
+        g = torch.Generator(device=dev).manual_seed(10)
+        K = args.rir_taps
+        rir = torch.randn(8, K, device=dev, generator=g) * torch.exp(
+            -6.9 * torch.arange(K, device=dev) / K)
+        recipes = {}
+        for k in ('', 'mel=80,dct=13,delta=2'):
+            base = ('wave:nfft=200,hop=100,norm=-5:4,' + k).rstrip(',')
+            recipes[(k + ' identity').strip()] = WaveRecipe.parse(base)
+            recipes[(k + ',reverb=%g' % args.reverb).lstrip(',')] = WaveRecipe.parse(
+                '%s,reverb=%r' % (base, args.reverb))
+    kr = WaveRecipe.parse('wave:nfft=200,hop=100,mel=80').mel_ksteps()
     mel_macs = sum(4 * (hi - lo + 1) * 16 for lo, hi in zip(kr[::2], kr[1::2]))   # per frame
     for P in (320, 32):
         ctrl = torch.zeros(4, dtype=torch.int64, device=dev)
@@ -123,10 +141,11 @@ def bench_pool(args):
         def wave(recipe, chunks):
             out = pool if not recipe.mel else torch.zeros(P, *recipe.out_hw(L), 8, device=dev,
                                                           dtype=torch.bfloat16)
+            kw = dict(rir=rir, rev_chunks=chunks) if recipe.reverb else dict(chunks=chunks)
 
             def fn():
                 _pool_wave(shard, bank if recipe.noise else None, labels, ctrl, out, pl, pi, P,
-                           B, 7, True, True, None, recipe, None, chunks=chunks)
+                           B, 7, True, True, None, recipe, None, **kw)
                 ctrl[0:1].add_(1)
             return fn
 
@@ -141,7 +160,9 @@ def bench_pool(args):
         variants = [('pool_spec_kernel identity', 0, spec), ('counter increment alone', 0, tick)]
         for name, r in recipes.items():
             sweep = {'full': (0, 2, 3, 4, 6, 11), 'mel=80 identity': (0, 3, 4, 6, 11)}
-            if args.speed or args.cmvn:
+            if args.reverb:             # (a reverb recipe's count is the pre-pass's)
+                sweep = {'reverb=%g' % args.reverb: (0, 2, 4, 8, 16)}
+            elif args.speed or args.cmvn:
                 sweep = {}
             elif args.delta:
                 sweep = {'mel=80,dct=13,delta=%d identity' % args.delta: (0, 2, 3, 4, 6, 11)}
@@ -161,6 +182,10 @@ def bench_pool(args):
                        'chunks': chunks, 'us': round(us, 3)}
                 if 'wave' in label:     # the padded GEMM: 176 frames x 200 x (2 x 112) columns
                     rec['gflop'] = round(P * 2 * 176 * 200 * 2 * 112 / 1e9, 3)
+                if 'reverb' in label:   # 63 tiles of 256 outputs, K16 + 16 padded taps
+                    rec['gflop_reverb'] = round(P * min(1.0, args.reverb) * 2 * 16128 * (
+                        (args.rir_taps + 15) // 16 * 16 + 16) / 1e9, 3)
+                    rec['rir_taps'] = args.rir_taps
                 if 'mel' in label:      # the K steps run per 16-band tile (+ 80 x 16 for dct)
                     rec['gflop_mel'] = round(P * 2 * 176 * (mel_macs + (
                         80 * 16 if 'dct' in label else 0)) / 1e9, 4)
@@ -265,6 +290,16 @@ def bench_banks(args):
         emit({'bench': 'speed_fir_banks', 'rate': rate, 'worst_lanes_per_bank_source': src,
               'worst_lanes_per_bank_table_pitch32': tab[32],
               'worst_lanes_per_bank_table_pitch33': tab[33]}, args.out)
+    # the reverb pre-pass (pool_reverb_kernel): the clip panel's B read over the 16 rows of a
+    # tile at `pad` pad words per 16, and the response's A read
+    for pad in (0, 1, 4):
+        clip = max(worst_b32(lambda lane: (lambda w: w + pad * (w >> 4))(
+            16 * (lane % 16) + 16 * so + 15 - 4 * si - lane // 16))
+            for so in range(4) for si in range(4))
+        emit({'bench': 'reverb_panel_banks', 'pad_per_16': pad,
+              'worst_lanes_per_bank_clip_read': clip}, args.out)
+    emit({'bench': 'reverb_rir_banks', 'worst_lanes_per_bank_rir_read': max(
+        worst_b32(lambda lane: 4 * si + lane // 16 + lane % 16) for si in range(4))}, args.out)
 
 
 def main():
@@ -280,6 +315,9 @@ def main():
     ap.add_argument('--speed', default='', help='LO:HI, pool mode: speed perturbation on / off')
     ap.add_argument('--cmvn', type=int, default=0, choices=(0, 1, 2),
                     help='pool mode: per-utterance CMVN on / off')
+    ap.add_argument('--reverb', type=float, default=0.0,
+                    help='pool mode: room-impulse reverberation with this probability on / off')
+    ap.add_argument('--rir-taps', type=int, default=2048)
     args = ap.parse_args()
     {'pool': bench_pool, 'step': bench_step, 'banks': bench_banks}[args.mode](args)
 

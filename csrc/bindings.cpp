@@ -838,7 +838,9 @@ PYBIND11_MODULE(_C, m) {
                         uintptr_t mel_tab, long long mel_floats, uintptr_t dct_tab,
                         long long dct_floats, std::vector<int> krange, int delta, int dwin,
                         uintptr_t speed_tab, long long speed_floats, int rq_lo, int rq_hi,
-                        int cmvn, uintptr_t feat, long long feat_floats) {
+                        int cmvn, uintptr_t feat, long long feat_floats, float reverb_p,
+                        uintptr_t rir, long long rir_floats, int Nr, int rir_k, uintptr_t rev,
+                        long long rev_floats, uintptr_t noise_f32, int rev_chunks) {
     if (!std::isfinite(gain_lo) || !std::isfinite(gain_hi) || gain_hi < gain_lo ||
         !std::isfinite(fill) || !std::isfinite(log_a) || !std::isfinite(log_b) ||
         !(noise_p >= 0.f && noise_p <= 1.f) || !(vol_max >= 0.f) || !std::isfinite(vol_max))
@@ -876,6 +878,15 @@ PYBIND11_MODULE(_C, m) {
     a.cmvn = cmvn;
     a.feat = P<float>(feat);
     a.feat_floats = feat_floats;
+    a.reverb_p = reverb_p;
+    a.rir = P<const float>(rir);
+    a.rir_floats = rir_floats;
+    a.Nr = Nr;
+    a.rir_k = rir_k;
+    a.rev = P<float>(rev);
+    a.rev_floats = rev_floats;
+    a.noise_f32 = P<const float>(noise_f32);
+    a.rev_chunks = rev_chunks;
     pool_wave_launch(a, S(st));
     check_launch("pool_wave");
   }, py::kw_only(), py::arg("shard"), py::arg("noise") = 0, py::arg("tab"),
@@ -893,7 +904,9 @@ PYBIND11_MODULE(_C, m) {
      py::arg("krange") = std::vector<int>(), py::arg("delta") = 0, py::arg("dwin") = 2,
      py::arg("speed_tab") = 0, py::arg("speed_floats") = 0, py::arg("rq_lo") = 0,
      py::arg("rq_hi") = 0, py::arg("cmvn") = 0, py::arg("feat") = 0,
-     py::arg("feat_floats") = 0);
+     py::arg("feat_floats") = 0, py::arg("reverb_p") = 0.f, py::arg("rir") = 0,
+     py::arg("rir_floats") = 0, py::arg("Nr") = 0, py::arg("rir_k") = 0, py::arg("rev") = 0,
+     py::arg("rev_floats") = 0, py::arg("noise_f32") = 0, py::arg("rev_chunks") = 0);
   m.def("is_sample", [](uintptr_t losses, uintptr_t ema, uintptr_t ctrl, uintptr_t idx, uintptr_t w,
                         uintptr_t meters, int Pn, int B, int group, int importance, float alpha,
                         float ema_alpha, uint32_t seed, uintptr_t st, int alias, uintptr_t gl,

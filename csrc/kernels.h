@@ -251,9 +251,25 @@ struct PoolWaveArgs {
   float* feat;                   // [P][R][feat_tp] fp32 workspace, 16-byte aligned
   long long feat_floats;
   int feat_tp;                   // (launcher) Tp = T rounded up to 4, the workspace's row pitch
+  // room-impulse reverberation (pool_reverb.hip): with probability reverb_p a slot's clip is
+  // convolved with a drawn row of the bank by pool_reverb_kernel, a pre-pass into rev[P][L], and
+  // the kernels above then read rev as a float32 shard indexed by slot; reverb_p = 0: off
+  float reverb_p;                // 0 < p <= 1
+  const float* rir;              // [Nr][rir_k] fp32 responses, causal, used as given
+  long long rir_floats;
+  int Nr, rir_k;                 // 1 <= rir_k <= REVERB_K_MAX
+  float* rev;                    // [P][L] fp32 workspace, 16-byte aligned
+  long long rev_floats;
+  const float* noise_f32;        // the noise bank of an int16 shard as fp32 (x / 32768, exact)
+  int rev_chunks;                // pre-pass output chunks per slot (grid.y); 0: the launcher's rule
+  int rev_on;                    // (launcher) the pre-pass runs: b.shard = rev, clip index = slot,
+                                 // params entry 15 is the pre-pass's
+  const void* rev_src;           // (launcher) the real shard, of dtype rev_src_f32
+  int rev_src_f32, rev_tiles, rev_u;   // (launcher) 256-output tiles per block, K rounded up to 16
 };
 constexpr float CMVN_VAR_FLOOR = 1e-5f;   // data/augment.py's CMVN_VAR_FLOOR (the biased variance)
 constexpr int CMVN_TP_MAX = 2048;         // two fp32 LDS rows for each of 4 waves in 64 KB
+constexpr int REVERB_K_MAX = 4096;        // taps of a response: the clip panel of one tile in LDS
 // throws std::invalid_argument on a shape the kernel cannot run (never a substitute)
 void pool_wave_launch(const PoolWaveArgs& a, hipStream_t st);
 int pool_wave_ksteps(int n_fft);   // K steps (of 4 samples) the table is padded to; 0: unsupported
@@ -265,6 +281,13 @@ void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st);
 // launch, so that a refusal launches nothing, and pool_cmvn_launch right behind it
 void pool_cmvn_check(PoolWaveArgs& a);
 void pool_cmvn_launch(const PoolWaveArgs& a, hipStream_t st);
+// the pre-pass of a reverb recipe (pool_reverb.hip).  pool_reverb_check, called by
+// pool_wave_launch behind the shared checks, throws on a bank, workspace or chunk count the
+// kernel cannot take and, when the pre-pass will run (reverb on and b.augment), points a at the
+// workspace and returns true; the route's launcher calls pool_reverb_launch right in front of
+// its own launch, behind its last check, so that a refusal launches nothing
+bool pool_reverb_check(PoolWaveArgs& a);
+void pool_reverb_launch(const PoolWaveArgs& a, hipStream_t st);
 
 struct IsSampleArgs {
   const float* losses;           // [P]

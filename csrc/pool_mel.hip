@@ -174,7 +174,7 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_mel_kernel(Pool
   const int halo = DELTA ? a.delta * a.dwin : 0;
   const int w0 = DELTA ? max(o0 - halo, 0) : o0;
   const int ntile = DELTA ? (min(o1 + halo, T) - w0 + 15) >> 4 : nown;
-  wave_stage_slot<S, SPEED>(a, s, src, w0 * a.hop, lds, tid, nthr);
+  wave_stage_slot<S, SPEED>(a, s, a.rev_on ? (uint32_t)slot : src, w0 * a.hop, lds, tid, nthr);
   __syncthreads();
 
   // ---- phase 1: DFT, table stationary, frames streaming; power into the panel
@@ -406,6 +406,7 @@ void pool_mel_launch(PoolWaveArgs a, int nk, hipStream_t st) {
   const size_t lds = ((size_t)a.panel_off + (size_t)panels(a.tiles_per_chunk)) * 4;
   const int threads = 64 * std::min(a.F16 / 16, nk > 64 ? 4 : 7);
   const dim3 grid(b.P, chunks);
+  if (a.rev_on) pool_reverb_launch(a, st);
   if (a.f32)
     launch_typed<float>(a, nk, grid, threads, lds, st);
   else

@@ -72,7 +72,8 @@ __global__ __launch_bounds__(NK > 64 ? 256 : 448) void pool_wave_kernel(PoolWave
   const int ntiles = (T + 15) >> 4;
   const int tile0 = blockIdx.y * a.tiles_per_chunk;
   const int ntile = min(a.tiles_per_chunk, ntiles - tile0);
-  wave_stage_slot<S, SPEED>(a, s, src, tile0 * 16 * a.hop, lds, tid, nthr);
+  wave_stage_slot<S, SPEED>(a, s, a.rev_on ? (uint32_t)slot : src, tile0 * 16 * a.hop, lds, tid,
+                            nthr);
   __syncthreads();
 
   // ---- table stationary, frames streaming
@@ -196,6 +197,7 @@ void pool_wave_launch(const PoolWaveArgs& a0, hipStream_t st) {
   if (a.tab_floats != (long long)4 * nk * 2 * a.F16)
     throw std::invalid_argument("pool_wave: the table holds 4*ksteps rows of 2*F16 floats");
   const bool speed = wave_speed_on(a);
+  pool_reverb_check(a);          // (with the pre-pass on: a.b.shard is its workspace from here)
   if (a.mel) return pool_mel_launch(a, nk, st);
   const int ntiles = (T + 15) / 16;
   // the stretch, and behind it the resampler's source panel and table
@@ -212,6 +214,7 @@ void pool_wave_launch(const PoolWaveArgs& a0, hipStream_t st) {
   const size_t lds = (size_t)need(a.tiles_per_chunk) * 4;
   const int waves = std::min(a.F16 / 16, nk > 64 ? 4 : 7);
   const dim3 grid(b.P, chunks);
+  if (a.rev_on) pool_reverb_launch(a, st);
   if (a.f32)
     launch_typed<float>(a, speed, nk, grid, waves * 64, lds, st);
   else

@@ -111,7 +111,7 @@ MA_DEV void wave_slot_header(const PoolWaveArgs& a, int slot, uint32_t src, cons
       p[11 + 2 * k] = (float)s.tw[k];
     }
     p[14] = SPEED ? (float)(s.rq - 65536) : 0.f;
-    p[15] = 0.f;
+    if (!a.rev_on) p[15] = 0.f;        // (a reverb pre-pass wrote 1 + rir, pool_reverb.hip)
   }
 }
 
@@ -201,7 +201,8 @@ MA_DEV void wave_stage_speed(const PoolWaveArgs& a, const WaveSlot& s, uint32_t 
   }
 }
 
-// the slot's staging: the resampler when the slot drew a rate other than 1
+// the slot's staging: the resampler when the slot drew a rate other than 1.  `src` is the clip's
+// row in a.b.shard: the shard index, or the slot when the shard is a reverb pre-pass's workspace
 template <typename S, bool SPEED>
 MA_DEV void wave_stage_slot(const PoolWaveArgs& a, const WaveSlot& s, uint32_t src, int q0,
                             float* lds, int tid, int nthr) {

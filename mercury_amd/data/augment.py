@@ -656,9 +656,22 @@ class SpecRecipe:
 
 # ---------------------------------------------------------------------- waveforms
 WAVE_PARAMS = 16     # shift, gain, noise_on, clip, off, vol, f0a, fwa, f0b, fwb, t0a, twa, t0b,
-#                      twb, rq - 65536 (speed), 0
+#                      twb, rq - 65536 (speed), 1 + rir (reverb on; else 0)
 SPEED_NT, SPEED_PH, SPEED_BETA = 32, 64, 8.0    # taps, phases, Kaiser beta of the resampler
 CMVN_VAR_FLOOR = 1e-5     # added to the biased variance of ``cmvn=2`` (csrc/kernels.h has its twin)
+REVERB_K_MAX = 4096       # taps of a room impulse response (csrc/kernels.h has its twin)
+
+
+def reverb_convolve(x, h):
+    """``y[i] = sum_{k <= min(K - 1, i)} h[k] x[i - k]`` for ``0 <= i < L``: the clip ``x[L]``
+    under the causal response ``h[K]``, the tail beyond L dropped.  fp64, a plain sum per
+    output (a Toeplitz product, in blocks of rows)."""
+    x, h = x.double(), h.double()
+    L, K = x.shape[0], h.shape[0]
+    rows = torch.cat([torch.zeros(K - 1, dtype=torch.float64), x]).unfold(0, K, 1)   # [L][K]
+    hf = h.flip(0)
+    step = max(1, (1 << 22) // K)
+    return torch.cat([rows[i:i + step] @ hf for i in range(0, L, step)])
 
 
 def speed_resample(xs, js, rq, table):
@@ -767,7 +780,19 @@ class WaveRecipe:
 
     ``preemph = C``, ``0 <= C < 1`` (off by default): Kaldi's per-frame pre-emphasis of each
     frame ``f[0..W)`` of the padded signal before the window, ``s[0] = f[0] - C f[0]``, ``s[n] =
-    f[n] - C f[n-1]``.  It is linear in the frame, so it lives in ``table()`` alone."""
+    f[n] - C f[n-1]``.  It is linear in the frame, so it lives in ``table()`` alone.
+
+    ``reverb = p``, ``0 < p <= 1`` (room-impulse reverberation; off by default), with a bank
+    ``rir [Nr][K]``, float32, ``1 <= K <= 4096``: one more Philox word (stream 0x5becd) turns it
+    on iff ``u01(r.x) < p`` and picks the response ``h = rir[r.y % Nr]``; ``params[15] = 1 + rir``
+    when on, else 0, and ``augment=False`` draws it off.  Step 0, before everything else:
+    ``xr[i] = sum_{k <= min(K - 1, i)} h[k] x[i - k]`` for ``0 <= i < L`` in fp32 (an int16 clip
+    as ``x / 32768`` first); the tail beyond L is lost.  Speed, shift, gain, the noise mix and
+    all later steps then run on ``xr`` in place of ``x``: a reverberant recording that is then
+    perturbed, so under ``speed`` the room is resampled with the speech.  Rows are used as
+    given: causal, ``h[0]`` the first tap, no normalisation, no peak alignment, finite values;
+    shorter responses are zero-padded by the user.  A slot that drew it off uses the clip itself
+    (``pool_reverb_kernel``, ``csrc/pool_reverb.hip``)."""
     n_fft: int = 200
     hop: int = 100
     shift: int = 0                                  # maximum shift in samples
@@ -789,12 +814,14 @@ class WaveRecipe:
     speed: Optional[Tuple[float, float]] = None     # (lo, hi) resampling rate (None: off)
     cmvn: int = 0                                   # 1: mean, 2: mean and variance, per clip
     preemph: float = 0.0                            # pre-emphasis coefficient C (0: off)
+    reverb: float = 0.0                             # probability of a room response (0: off)
 
     def __post_init__(self):
         s = object.__setattr__
         for k in ('n_fft', 'hop', 'shift', 'mel', 'sr', 'dct', 'delta', 'dwin', 'lifter', 'cmvn'):
             s(self, k, int(getattr(self, k)))
         s(self, 'preemph', float(self.preemph))
+        s(self, 'reverb', float(self.reverb))
         s(self, 'fmin', float(self.fmin))
         s(self, 'fmax', None if self.fmax is None else float(self.fmax))
         s(self, 'fmask', _mask(self.fmask, 'fmask'))
@@ -856,12 +883,15 @@ class WaveRecipe:
             raise ValueError('WaveRecipe: cmvn needs mel > 0 (no CMVN on the linear bins)')
         if not 0 <= self.preemph < 1:
             raise ValueError('WaveRecipe: preemph is 0 <= C < 1, got %r' % self.preemph)
+        if not 0 <= self.reverb <= 1:
+            raise ValueError('WaveRecipe: reverb is a probability 0 < p <= 1 (0: off), got %r'
+                             % self.reverb)
 
     @classmethod
     def parse(cls, spec):
         """``wave:nfft=200,hop=100,shift=1600,gain=0.8:1.2,noise=0.8x0.1,eps=1e-6,norm=-5:4,
         fmask=2x10,tmask=2x20,fill=0,mel=80,sr=16000,fmin=0,fmax=8000,dct=13,delta=2,dwin=2,
-        lifter=22,speed=0.9:1.1,cmvn=2,preemph=0.97`` (the ``wave:`` prefix is optional here)."""
+        lifter=22,speed=0.9:1.1,cmvn=2,preemph=0.97,reverb=0.5`` (the ``wave:`` prefix is optional here)."""
         spec = spec.strip()
         if spec.startswith('wave:'):
             spec = spec[5:]
@@ -890,7 +920,7 @@ class WaveRecipe:
                     raise ValueError('WaveRecipe.parse: %s is A:B, got %r' % (k, v))
                 else:
                     kw[k] = (float(g[0]), float(g[1]))
-            elif k in ('fill', 'eps', 'fmin', 'preemph'):
+            elif k in ('fill', 'eps', 'fmin', 'preemph', 'reverb'):
                 kw[k] = float(v)
             elif k == 'fmax':
                 kw[k] = None if v in ('', 'none') else float(v)
@@ -926,6 +956,8 @@ class WaveRecipe:
             out.append('cmvn=%d' % self.cmvn)
         if self.preemph:
             out.append('preemph=%r' % self.preemph)
+        if self.reverb:
+            out.append('reverb=%r' % self.reverb)
         return 'wave:' + ','.join(out)
 
     @property
@@ -933,7 +965,7 @@ class WaveRecipe:
         """No augmentation on: every draw is the identity whatever the random words."""
         return (self.shift == 0 and self.gain is None and self.noise is None
                 and 0 in self.fmask and 0 in self.tmask
-                and self.speed_rq() in (None, (65536, 65536)))
+                and self.speed_rq() in (None, (65536, 65536)) and not self.reverb)
 
     def out_hw(self, L):
         """(R, T): rows and frames of an L-sample clip, the network's input size.  R is ``dct``
@@ -951,9 +983,17 @@ class WaveRecipe:
         return (1.0, 0.0) if self.norm is None else (1.0 / self.norm[1],
                                                      -self.norm[0] / self.norm[1])
 
-    def check(self, L, noise_shape=None):
-        """Raise unless the recipe fits L-sample clips and a noise bank of shape (Nn, Ln)
-        (``None``: no bank); names the field that does not."""
+    def check(self, L, noise_shape=None, rir_shape=None):
+        """Raise unless the recipe fits L-sample clips, a noise bank of shape (Nn, Ln) and an
+        RIR bank of shape (Nr, K) (``None``: no bank); names the field that does not."""
+        if self.reverb and rir_shape is None:
+            raise ValueError('WaveRecipe: reverb=%r needs an RIR bank [Nr][K]' % self.reverb)
+        if rir_shape is not None:
+            if not self.reverb:
+                raise ValueError('WaveRecipe: an RIR bank needs reverb=p')
+            if len(rir_shape) != 2 or rir_shape[0] < 1 or not 1 <= rir_shape[1] <= REVERB_K_MAX:
+                raise ValueError('WaveRecipe: RIR bank must be [Nr >= 1][1 <= K <= %d], got %s'
+                                 % (REVERB_K_MAX, tuple(rir_shape)))
         if L <= self.n_fft // 2:
             raise ValueError('WaveRecipe: n_fft %d needs clips longer than n_fft/2, got L = %d'
                              % (self.n_fft, L))
@@ -970,9 +1010,9 @@ class WaveRecipe:
             raise ValueError('WaveRecipe: noise bank must be [Nn >= 1][Ln >= L = %d], got %s'
                              % (L, tuple(noise_shape)))
 
-    def draw(self, L, noise_shape=None, generator=None):
+    def draw(self, L, noise_shape=None, generator=None, rir_shape=None):
         """One slot's draws from torch's RNG, in the kernel's ranges and ``params`` layout."""
-        self.check(L, noise_shape)
+        self.check(L, noise_shape, rir_shape)
 
         def ri(n):
             return int(torch.randint(0, n, (1,), generator=generator).item())
@@ -995,6 +1035,8 @@ class WaveRecipe:
         if self.speed is not None:
             lo, hi = self.speed_rq()
             p[14] = float(lo + ri(hi - lo + 1) - 65536)
+        if self.reverb and ru() < self.reverb:
+            p[15] = float(1 + ri(rir_shape[0]))
         return p
 
     def identity_params(self):
@@ -1114,11 +1156,11 @@ class WaveRecipe:
         return out
 
     # ---------------------------------------------------------------- CPU reference
-    def reference(self, x, noise, params, dtype=torch.bfloat16):
+    def reference(self, x, noise, params, dtype=torch.bfloat16, rir=None):
         """The recipe on one clip ``x[L]`` (int16 or float) with explicit draws ``params``
-        (``WAVE_PARAMS`` values, the kernel's layout) and the noise bank ``noise`` ([Nn][Ln] or
-        None) -> [R][T][8] ``dtype``, the pool's layout (``out_hw``).  fp64 from step 1 on, then one
-        rounding to ``dtype``."""
+        (``WAVE_PARAMS`` values, the kernel's layout), the noise bank ``noise`` ([Nn][Ln] or
+        None) and the RIR bank ``rir`` ([Nr][K] or None) -> [R][T][8] ``dtype``, the pool's layout
+        (``out_hw``).  fp64 from step 0 on, then one rounding to ``dtype``."""
         def f64(t):
             t = torch.as_tensor(t)
             return t.double() / 32768 if t.dtype == torch.int16 else t.double()
@@ -1126,13 +1168,18 @@ class WaveRecipe:
         if x.dim() != 1:
             raise ValueError('reference: the clip must be [L]')
         L, W, hop = x.shape[0], self.n_fft, self.hop
-        self.check(L, None if noise is None else tuple(noise.shape))
+        self.check(L, None if noise is None else tuple(noise.shape),
+                   None if rir is None else tuple(rir.shape))
         p = [float(v) for v in params]
         if len(p) != WAVE_PARAMS:
             raise ValueError('reference: params has %d values' % WAVE_PARAMS)
         s = int(p[0])
         j = torch.arange(L)
         xs = f64(x)
+        if p[15]:         # step 0: the clip under response 1 + rir, the tail beyond L dropped
+            if rir is None:
+                raise ValueError('reference: params has reverb on but there is no RIR bank')
+            xs = reverb_convolve(xs, torch.as_tensor(rir)[int(p[15]) - 1])
         if p[14]:         # the clip at rate rq; rq = 65536 is x[js] itself, as in the kernel
             if self.speed is None:
                 raise ValueError('reference: params has a rate but the recipe has no speed')

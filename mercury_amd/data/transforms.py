@@ -301,17 +301,21 @@ class WaveSpectrogram(object):
     ``recipe.out_hw(L)``.
     The draws come from torch's RNG (``generator``) through ``WaveRecipe.draw``, the arithmetic
     is ``WaveRecipe.reference``; ``noise`` is the bank [Nn][Ln] a ``noise=`` recipe mixes from,
+    ``rir`` the float32 bank [Nr][K] a ``reverb=`` recipe convolves with,
     ``augment=False`` the evaluation transform (identity draws).  The eager ``Trainer`` runs it
     as the dataset's transform on any device; ``Config(augment='dataset')`` hands its recipe to
     the native engine's pool build (``pool_wave_kernel``) instead."""
 
-    def __init__(self, recipe, noise=None, generator=None, augment=True):
+    def __init__(self, recipe, noise=None, generator=None, augment=True, rir=None):
         from .augment import WaveRecipe
         self.recipe = WaveRecipe.parse(recipe) if isinstance(recipe, str) else recipe
         if not isinstance(self.recipe, WaveRecipe):
             raise ValueError('WaveSpectrogram: expected a WaveRecipe or its spec string, got %r'
                              % (recipe,))
         self.noise = None if noise is None else torch.as_tensor(noise)
+        self.rir = None if rir is None else torch.as_tensor(rir)
+        if self.rir is not None and self.rir.dtype != torch.float32:
+            raise ValueError('WaveSpectrogram: the RIR bank is float32, got %s' % self.rir.dtype)
         self.generator, self.augment = generator, augment
         self.last = None                 # the last call's draws (WaveRecipe's params layout)
 
@@ -319,10 +323,11 @@ class WaveSpectrogram(object):
         x = torch.as_tensor(x)
         if self.augment:
             shape = None if self.noise is None else tuple(self.noise.shape)
-            self.last = self.recipe.draw(x.shape[0], shape, self.generator)
+            self.last = self.recipe.draw(x.shape[0], shape, self.generator,
+                                         None if self.rir is None else tuple(self.rir.shape))
         else:
             self.last = self.recipe.identity_params()
-        y = self.recipe.reference(x, self.noise, self.last, dtype=torch.float32)
+        y = self.recipe.reference(x, self.noise, self.last, dtype=torch.float32, rir=self.rir)
         return y[:, :, 0].unsqueeze(0).contiguous()
 
     def __repr__(self):

@@ -173,6 +173,7 @@ class NativeEngine(object):
         #                                  [P][12] for a SpecRecipe, [P][16] with rrc / jitter
         #                                  and for a WaveRecipe
         self.noise = None                # [Nn][Ln] background clips of a WaveRecipe (set_shard)
+        self.rir = None                  # [Nr][K] float32 room responses of a reverb= recipe
         self.seed = seed
         self.alpha, self.ema_alpha, self.importance = alpha, ema_alpha, importance
         self.world_size = world_size
@@ -846,7 +847,8 @@ class NativeEngine(object):
             if x.dim() != 2 or x.dtype not in (torch.int16, torch.float32):
                 raise ValueError('a WaveRecipe needs an int16 or float32 shard [N][L], got %s %s'
                                  % (x.dtype, tuple(x.shape)))
-            recipe.check(x.shape[1], None if self.noise is None else tuple(self.noise.shape))
+            recipe.check(x.shape[1], None if self.noise is None else tuple(self.noise.shape),
+                         None if self.rir is None else tuple(self.rir.shape))
             if recipe.out_hw(x.shape[1]) != (self.H, self.W):
                 raise ValueError('the WaveRecipe makes %dx%d spectrograms of %d-sample clips but '
                                  'the engine was built for image_hw=%s'
@@ -886,11 +888,19 @@ class NativeEngine(object):
             ops.nchw_to_nhwc8(blk, out[s0:s0 + step])
         return out
 
-    def set_shard(self, images, labels, noise=None):
+    def set_shard(self, images, labels, noise=None, rir=None):
         """Keep this rank's training shard resident in HBM: uint8 [Ns][H][W][3] images, or
         float [Ns][C][H][W] inputs pre-converted to NHWC bf16 (planar bf16 under a SpecRecipe),
         or -- under a WaveRecipe -- raw clips [Ns][L], int16 or float32, in their own dtype,
-        with the ``noise`` bank [Nn][Ln] of the same dtype a ``noise=`` recipe mixes from."""
+        with the ``noise`` bank [Nn][Ln] of the same dtype a ``noise=`` recipe mixes from and
+        the float32 ``rir`` bank [Nr][K] a ``reverb=`` recipe convolves with."""
+        if rir is not None:
+            if not isinstance(self.augment, WaveRecipe):
+                raise ValueError('rir: an RIR bank belongs to a WaveRecipe')
+            h = torch.as_tensor(np.ascontiguousarray(rir)) if not torch.is_tensor(rir) else rir
+            if h.dtype != torch.float32:
+                raise ValueError('RIR bank is %s: it is always float32' % h.dtype)
+            self.rir = h.to(self.device).contiguous()
         if noise is not None:
             if not isinstance(self.augment, WaveRecipe):
                 raise ValueError('noise: a noise bank belongs to a WaveRecipe')
@@ -911,6 +921,11 @@ class NativeEngine(object):
             if self.augment.cmvn:                    # the pool's and the plain batch's workspace
                 for n in (self.P, self.B):
                     ops.importance.pool_cmvn_workspace(self.augment, n, x.shape[1], self.device)
+            if self.augment.reverb:                  # the pre-pass's workspaces, the fp32 noise
+                for n in (self.P, self.B):
+                    ops.importance.pool_reverb_workspace(n, x.shape[1], self.device)
+                if self.noise is not None and self.noise.dtype == torch.int16:
+                    ops.importance.pool_noise_f32(self.noise)
         if self.augment is not None and self.aug_params is None:
             n = SPEC_PARAMS if isinstance(self.augment, SpecRecipe) else \
                 WAVE_PARAMS if isinstance(self.augment, WaveRecipe) else \
@@ -969,7 +984,7 @@ class NativeEngine(object):
             # (epoch-shuffled, augmented), no pool forward, unit weights
             ops.pool_build(self.shard, self.shard_labels, self.ctrl, sm.input, sm.label,
                            sm.index, self.B, self.B, self.seed, recipe=self.augment,
-                           params=self.aug_params, noise=self.noise)
+                           params=self.aug_params, noise=self.noise, rir=self.rir)
             self.ctrl[0:1].add_(1)
             self.idx.copy_(self._arange_b)
             self.isw.fill_(1.0)
@@ -983,7 +998,7 @@ class NativeEngine(object):
         ops.pool_build(self.shard, self.shard_labels, self.ctrl, sm.input, sm.label, sm.index,
                        self.P, self.B, self.seed, zero=sm.stats_arena,
                        shuffle=self.sampler != 'groupwise', recipe=self.augment,
-                       params=self.aug_params, noise=self.noise)
+                       params=self.aug_params, noise=self.noise, rir=self.rir)
         # (the scoring convs keep their full occupancy: reserving extra LDS per scoring block
         # so train blocks fit beside them measured 1.70-2.21 ms/step vs 1.65 -- in the
         # concurrent step the GPU is throughput-bound, bench/ab_env.sh)
@@ -1559,7 +1574,7 @@ class NativeEngine(object):
             if wave:
                 ops.pool_build(imgs[done:done + b], labs[done:done + b], ctrl, m.input, m.label,
                                m.index, b, b, self.seed, augment=False, shuffle=False,
-                               recipe=recipe, noise=self.noise)
+                               recipe=recipe, noise=self.noise, rir=self.rir)
             elif recipe is not None:
                 ops.pool_build(imgs[done:done + b], labs[done:done + b], ctrl, m.input, m.label,
                                m.index, b, b, self.seed, shuffle=False, recipe=recipe)
@@ -1707,7 +1722,10 @@ class NativeTrainer(Trainer):
                 bank = getattr(ds, 'noise', None)
                 if bank is None:
                     bank = getattr(getattr(ds, 'transform', None), 'noise', None)
-                self.engine.set_shard(x, y, noise=bank)
+                rir = getattr(ds, 'rir', None)
+                if rir is None:
+                    rir = getattr(getattr(ds, 'transform', None), 'rir', None)
+                self.engine.set_shard(x, y, noise=bank, rir=rir)
             except ValueError:
                 self.engine.close()
                 raise

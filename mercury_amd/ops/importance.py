@@ -10,7 +10,7 @@ from ..data.transforms import CIFAR_MEAN, CIFAR_STD
 
 def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, pad=4,
                flip=True, augment=True, mean=CIFAR_MEAN, std=CIFAR_STD, shuffle=True, zero=None,
-               recipe=None, params=None, force_augment_kernel=False, noise=None):
+               recipe=None, params=None, force_augment_kernel=False, noise=None, rir=None):
     """Build a P-sample presample pool on device from either the uint8 image shard
     [Ns][H][W][3] (crop/flip/normalise on the fly) or a pre-converted bf16 shard
     [Ns][H][W][8] (non-image inputs: plain gather, no augmentation).  ``zero``: an fp32
@@ -45,15 +45,21 @@ def pool_build(shard, labels, ctrl, pool, pool_label, pool_index, P, batch, seed
     recipe then runs two launches: ``pool_wave_mel_kernel`` into the workspace, ``pool_cmvn_kernel``
     from it into the pool): inside a graph capture only after such a call or ``pool_wave_table`` /
     ``pool_mel_tables`` / ``pool_speed_table`` / ``pool_cmvn_workspace``
-    (``NativeEngine.set_shard`` makes them).  ``preemph`` only changes the DFT table."""
+    (``NativeEngine.set_shard`` makes them).  ``preemph`` only changes the DFT table.
+    A ``reverb`` recipe takes its float32 bank ``rir`` [Nr][K], K <= 4096, and with ``augment``
+    on runs ``pool_reverb_kernel`` (``csrc/pool_reverb.hip``) in front: each slot's clip,
+    convolved with a drawn response or copied, goes into the fp32 workspace
+    ``pool_reverb_workspace(P, L, device)`` and the launches above read it in place of the shard.
+    That workspace, and for an int16 shard the noise bank's fp32 copy (``pool_noise_f32``), are
+    made by the first such build (outside a capture)."""
     _chk(labels, torch.int64, 'labels')
     if isinstance(recipe, WaveRecipe):
         if force_augment_kernel:
             raise ValueError('force_augment_kernel belongs to an AugmentRecipe')
         return _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batch,
-                          seed, augment, shuffle, zero, recipe, params)
-    if noise is not None:
-        raise ValueError('noise: a noise bank belongs to a WaveRecipe')
+                          seed, augment, shuffle, zero, recipe, params, rir=rir)
+    if noise is not None or rir is not None:
+        raise ValueError('noise / rir: a noise or RIR bank belongs to a WaveRecipe')
     if shard.dim() == 2:
         raise ValueError('shard is [Ns][L] raw clips: that needs a WaveRecipe')
     if isinstance(recipe, SpecRecipe):
@@ -202,14 +208,43 @@ def pool_cmvn_workspace(recipe, P, L, device):
     return _CMVN_FEAT[key]
 
 
+_REVERB_WS = {}      # (P, L, device) -> the fp32 workspace of a reverb recipe's pre-pass
+_NOISE_F32 = {}      # (data_ptr, shape, device) -> (the int16 noise bank, its fp32 copy / 32768)
+
+
+def pool_reverb_workspace(P, L, device):
+    """The fp32 workspace ``[P][L]``, indexed by pool slot, into which a ``reverb`` recipe's
+    pre-pass writes each slot's (convolved) clip, one per shape and device (never allocated
+    inside a capture: ``NativeEngine.set_shard`` makes it).  Pool builds of one shape share it,
+    which is safe on one stream, where the launches are ordered."""
+    device = torch.device(device)
+    if device.index is None:             # 'cuda' and 'cuda:0' name one workspace
+        device = torch.device(device.type, torch.cuda.current_device())
+    key = (P, L, str(device))
+    if key not in _REVERB_WS:
+        _REVERB_WS[key] = torch.empty(P, L, dtype=torch.float32, device=device)
+    return _REVERB_WS[key]
+
+
+def pool_noise_f32(noise):
+    """An int16 noise bank as float32 ``x / 32768`` (exact): what the wave kernels mix from when
+    they read a reverb pre-pass's fp32 workspace.  Made once per bank, which the cache keeps
+    alive; a bank changed in place needs a new tensor."""
+    key = (noise.data_ptr(), tuple(noise.shape), str(noise.device))
+    if key not in _NOISE_F32:
+        _NOISE_F32[key] = (noise, noise.to(torch.float32) / 32768)
+    return _NOISE_F32[key][1]
+
+
 def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batch, seed, augment,
-               shuffle, zero, recipe, params, chunks=0):
+               shuffle, zero, recipe, params, chunks=0, rir=None, rev_chunks=0):
     if shard.dtype not in (torch.int16, torch.float32) or shard.dim() != 2:
         raise ValueError('a WaveRecipe needs an int16 or float32 shard [Ns][L], got %s %s'
                          % (shard.dtype, tuple(shard.shape)))
     _chk(shard, shard.dtype, 'shard')
     Ns, L = int(shard.shape[0]), int(shard.shape[1])
-    recipe.check(L, None if noise is None else tuple(noise.shape))
+    recipe.check(L, None if noise is None else tuple(noise.shape),
+                 None if rir is None else tuple(rir.shape))
     if noise is not None:
         if noise.dtype != shard.dtype:
             raise ValueError('noise bank is %s but the shard is %s' % (noise.dtype, shard.dtype))
@@ -235,6 +270,16 @@ def _pool_wave(shard, noise, labels, ctrl, pool, pool_label, pool_index, P, batc
     if recipe.cmvn:
         feat = pool_cmvn_workspace(recipe, P, L, shard.device)
         mel.update(cmvn=recipe.cmvn, feat=ptr(feat), feat_floats=feat.numel())
+    if recipe.reverb:
+        if rir.dtype != torch.float32:
+            raise ValueError('RIR bank is %s: it is always float32' % rir.dtype)
+        _chk(rir, torch.float32, 'rir')
+        rev = pool_reverb_workspace(P, L, shard.device)
+        mel.update(reverb_p=recipe.reverb, rir=ptr(rir), rir_floats=rir.numel(),
+                   Nr=rir.shape[0], rir_k=rir.shape[1], rev=ptr(rev), rev_floats=rev.numel(),
+                   rev_chunks=rev_chunks)
+        if noise is not None and noise.dtype == torch.int16:
+            mel.update(noise_f32=ptr(pool_noise_f32(noise)))
     glo, ghi = recipe.gain or (1.0, 1.0)
     p, vol = recipe.noise or (0.0, 0.0)
     a, b = recipe.affine()
